@@ -1,6 +1,7 @@
 """Benchmark: the frame-differencing hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full                           # + CPU baseline, five runs, roofline, copy rate
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
     python bench.py --width 3840 --height 2160       # configs[2]: 4K FD feed
     python bench.py --path of                        # configs[4]: 1080p OF (Farneback) path
@@ -24,11 +25,18 @@ dvc_fd_step per frame instead, 50 k, each call one HIP graph launch).
 Feeds shard one per GPU with no data-path collective ("scaling": "weak");
 RCCL carries only the end-of-run aggregate stats and the max-over-ranks time.
 
-Timing: ``--runs`` (5) timed runs of exactly ``--steps`` steps each, each
-bracketed by a barrier and a device sync; ``value`` is the median run (max over
-ranks per run), every run's value under ``timing``. ``ranks`` records the
-world size the process group saw and every rank's own frame count.
+A plain run does what the headline figure needs and no more: set-up, ``--warmup``
+steps, one timed run of exactly ``--steps`` steps bracketed by a barrier and a
+device sync, the result line (``value``; ``ms_per_step``: the milliseconds one
+timed step took). ``--dump-outputs DIR`` writes, after the timed steps, what
+the last of them computed (both output sequences and the run's counters) as
+``DIR/<name>.npy``: the inputs are the same from run to run, so two builds can
+be compared output for output. ``ranks`` records the world size the process
+group saw and every rank's own frame count.
 
+``--full`` adds everything else. Timing: ``--runs`` (5) timed runs of
+``--steps`` steps each; ``value`` is the median run (max over ranks per run),
+every run's value under ``timing``.
 Extra JSON fields: ``roofline`` for the dominant kernel (FD: the fused k_front:
 hipEvent time per launch on the front stream where it runs, in a second pass of
 the same steps; k_out on the back stream when the one-pass output stage runs —
@@ -161,6 +169,37 @@ def copy_bandwidth(local: int, nbytes=2 << 30, reps=20):
     return max(plain, nt), {"plain": round(plain, 1), "nontemporal": round(nt, 1)}
 
 
+DUMP_SEED = 20240607
+DUMP_ELEMS = 12 << 20          # float32 elements over all frame outputs of a run: 48 MiB
+
+
+def dump_outputs(path: str, arrays: dict, rank: int = 0, world: int = 1):
+    """Write the last timed step's outputs as ``path/<name>.npy`` (float32; the
+    ``stats`` counters float64). An output of P frames larger than its share of
+    DUMP_ELEMS is sampled: the same number of elements of every frame, at
+    positions drawn per frame from a generator seeded by DUMP_SEED alone, so two
+    runs with the same arguments write the same elements, as a (P, k) array.
+    Ranks above 0 write ``<name>_rank<r>.npy``."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    frames = [k for k, a in arrays.items() if a.ndim > 1]
+    share = DUMP_ELEMS // max(1, len(frames) * world)
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, a in arrays.items():
+        if a.ndim > 1 and int(np.prod(a.shape)) > share:
+            flat = a.reshape(a.shape[0], -1)
+            idx = rng.integers(0, flat.shape[1], size=(a.shape[0], max(1, share // a.shape[0])))
+            if isinstance(a, torch.Tensor):
+                a = torch.gather(flat, 1, torch.from_numpy(idx).to(a.device))
+            else:
+                a = np.take_along_axis(flat, idx, 1)
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        out = np.asarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), out)
+
+
 def run_cpu_baseline(args):
     """One host core (the oracle is single-threaded per feed), and beside it every
     available core up to the box's CPU share, one feed per core."""
@@ -222,8 +261,15 @@ def main():
                          "outputs, so a fused-front batch waits for the fix-up of the batch two before it")
     ap.add_argument("--ktime-seconds", type=float, default=6.0,
                     help="minimum device time of the hipEvent pass that times the dominant kernel")
-    ap.add_argument("--runs", type=int, default=5,
-                    help="timed runs of --steps steps each; the line reports the median run (SURVEY.md §8d)")
+    ap.add_argument("--runs", type=int, default=0,
+                    help="timed runs of --steps steps each; the line reports the median run (SURVEY.md §8d); "
+                         "0: one run, five with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: five timed runs instead of one, the CPU baseline, the "
+                         "dominant kernel's hipEvent pass and roofline, and the measured copy rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32; a fixed, seeded sample of the output frames, see dump_outputs)")
     args = ap.parse_args()
 
     import numpy as np
@@ -238,7 +284,7 @@ def main():
     # the CPU baseline (rank 0 at N=1 only) runs first, in fresh processes, so the
     # GPU phase below is one contiguous stretch of device work
     cpu_base = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu_base = run_cpu_baseline(args)
     # DVC_BENCH_ONE_DEVICE=1: rehearse the N > 1 flow on a one-GPU box (every
     # rank on cuda:0, gloo for the end-of-run reduction; RCCL refuses two ranks
@@ -364,7 +410,7 @@ def main():
     # --runs timed runs of exactly --steps steps each, every one bracketed by a
     # barrier + device sync on both sides; the line reports the median run
     # (max over ranks per run), all runs listed beside it
-    runs = max(1, args.runs)
+    runs = args.runs if args.runs > 0 else (5 if args.full else 1)
     elapsed_runs = []
     st0 = [w.stats() for w in ws]   # counters before the timed runs (prime + warmup)
     has_gs = not of and hasattr(ws[0]._lib, "dvc_fd_graph_stats")
@@ -389,21 +435,30 @@ def main():
     st = {k: sum(x[k] - x0[k] for x, x0 in zip(sts, st0)) / runs for k in sts[0]}
     for w in ws:
         w.close()
+    if args.dump_outputs:
+        names = ("mask", "compressed") if of else ("overlay", "compressed")
+        last = {}
+        for f in range(F):
+            for name, arr in zip(names, inputs[f][1][(step_no[f] - 1) % len(inputs[f][1])]):
+                last[name if F == 1 else f"{name}_feed{f}"] = arr
+        last["stats"] = np.array([st[k] for k in ("frames", "motion_px", "components", "static_blocks")], np.float64)
+        dump_outputs(args.dump_outputs, last, rank, world)
 
-    # dominant kernel: hipEvent-timed launches (the fused front on the front
+    # --full, dominant kernel: hipEvent-timed launches (the fused front on the front
     # stream or k_out on the back stream / k_flow level 0 on the flow stream) of
     # feed 0 alone, same steps; at least ~--ktime-seconds of device time, so the
     # GPU phase is long enough for an outside utilisation sampler to see
-    wk = make_worker(0, ktiming=True)
-    run_steps([wk], 1)
-    wk.ktime(reset=True)
-    step_s = sorted(elapsed_runs)[len(elapsed_runs) // 2] / max(args.steps, 1)
-    ksteps = max(1, min(args.steps, 10), int(args.ktime_seconds / max(step_s, 1e-6)))
-    run_steps([wk], ksteps)
-    kms, kn = wk.ktime()
-    kkernel = wk.ktime_kernel()   # the library reports the kernel it launched (FD: front / k_out; OF: level 0)
-    wk.close()
-    kframes = ksteps * P
+    if args.full:
+        wk = make_worker(0, ktiming=True)
+        run_steps([wk], 1)
+        wk.ktime(reset=True)
+        step_s = sorted(elapsed_runs)[len(elapsed_runs) // 2] / max(args.steps, 1)
+        ksteps = max(1, min(args.steps, 10), int(args.ktime_seconds / max(step_s, 1e-6)))
+        run_steps([wk], ksteps)
+        kms, kn = wk.ktime()
+        kkernel = wk.ktime_kernel()   # the library reports the kernel it launched (FD: front / k_out; OF: level 0)
+        wk.close()
+        kframes = ksteps * P
 
     # the end-of-run collective (RCCL at N > 1; feeds.reduce_runs): counters
     # summed, each run's time maxed, every rank's own frame count
@@ -424,7 +479,6 @@ def main():
     value = frames_total * W * H / elapsed_max / 1e6
 
     if rank == 0:
-        avg_ms = kms / max(kn, 1)
         res = f"{W}x{H}" if (W, H) != (1920, 1080) else "1080p"
         workload = f"{args.path}_{res}_single_feed_per_gpu" if F == 1 else f"{args.path}_{res}_{F}_feeds_per_gpu"
         if host_io:
@@ -441,23 +495,6 @@ def main():
             workload += "_direct_sums"
         if not of and (args.block_size, args.kernel_size, args.release_factor) != (4, 7, 0.5):
             workload += f"_b{args.block_size}_k{args.kernel_size}_r{args.release_factor:g}"
-        if of:   # kn counts level-0 flow launches (iterations per batch)
-            kname = kkernel   # the level-0 kernel the library launched (dvc_of_ktime_kernel)
-            per_launch_frames = kframes * 2 / max(kn, 1)
-            bytes_per_launch = OF_FLOW_BYTES_PER_PX * W * H * per_launch_frames
-            traffic = pmc_traffic(os.path.join(ROOT, "profiles", "pmc_summary_of.json"), kname, workload,
-                                  per_launch_frames)
-        else:
-            kname = kkernel
-            per_launch_frames = kframes / max(kn, 1)
-            # I420 outputs: 1.5 B/px each instead of 3; 4:2:0 input surfaces are read
-            # in place (1.5 B/px instead of the BGR frame's 3)
-            back = BACK_BYTES_PER_PX_FRAME - (3.0 if args.out_format == "I420" else 0.0) - (1.5 if yuv else 0.0)
-            per_launch = FRONT_FUSED_BYTES_PER_PX_LAUNCH if kname == "k_front_fused" else BACK_BYTES_PER_PX_LAUNCH
-            bytes_per_launch = (back * kframes + per_launch * kn) * W * H / max(kn, 1)
-            traffic = pmc_traffic(os.path.join(ROOT, "profiles", "pmc_summary.json"),
-                                  "k_front" if kname == "k_front_fused" else "k_out", workload, per_launch_frames)
-        achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9
         # SURVEY §8d's per-pixel bytes for this configuration: frame in (BGR 3 / 4:2:0
         # 1.5), state 4, outputs 2 x (BGR 3 / I420 1.5)
         pipe = OF_PIPE_BYTES_PER_PX if of else (PIPE_BYTES_PER_PX - (1.5 if yuv else 0.0)
@@ -491,46 +528,65 @@ def main():
                        "fps_per_gpu": round(args.steps * P * F / elapsed_max, 1),
                        "pipeline_bytes_per_px": pipe,
                        "pipeline_GBps_per_gpu": round(pipe * args.steps * P * F * W * H / elapsed_max / 1e9, 1)},
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "algorithmic_bytes_per_launch": int(bytes_per_launch),
-                         "frames_per_launch": round(per_launch_frames, 2),
-                         "avg_launch_us": round(avg_ms * 1e3, 2), "launches_timed": kn,
-                         "timed_with": "feed 0 alone"},
             "stats": {"scope": "one timed run, all ranks", "frames": int(vec[0]), "motion_px": int(vec[1]),
                       "components": int(vec[2]), "static_blocks": int(vec[3]), "frames_nominal": frames_nominal},
             "timing": {"runs": runs, "reported": "median run", "steps_per_run": args.steps,
                        "value_per_run": [round(frames_total * W * H / t / 1e6, 2) for t in
-                                         tmax],
-                       "ktime_pass": {"steps": ksteps, "launches": kn}},
+                                         tmax]},
             "ranks": ranks,
         }
-        if traffic is not None:
-            line["roofline"]["traffic_source"] = (
-                "committed rocprofv3 PMC profile of the same workload and launch size (2 x FETCH_SIZE + "
-                "WRITE_SIZE, tools/profile_round.sh): profiles/" + ("pmc_summary_of.json" if of else "pmc_summary.json"))
-        # the same kernel's bytes (and the pipeline's) against this box's measured copy rate
-        cp_gbs, cp_detail = copy_bandwidth(local)
-        line["roofline"]["copy"] = {"GBps": round(cp_gbs, 1), "frac": round(achieved / cp_gbs, 4),
-                                    "pipeline_frac": round(line["config"]["pipeline_GBps_per_gpu"] / cp_gbs, 4),
-                                    "kernel": "dvc_copy_rate: hand-written 16 B/lane copy of 2 GiB", **cp_detail}
-        if of:   # k_flow's binding axis is the VALU (serial f64 recurrences), not HBM
-            px_it = W * H * per_launch_frames
-            flops = px_it * (OF_FLOW_F32_FLOPS_PER_PX + 2 * OF_FLOW_F64_FLOPS_PER_PX)
-            tf = flops / (avg_ms * 1e-3) / 1e12
-            hbm = line["roofline"]
-            line["roofline"] = {"bound": "valu", "kernel": kname, "achieved": round(tf, 3),
-                                "peak": FP32_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s (FP32-equivalent)",
-                                "frac": round(tf / FP32_VECTOR_PEAK_TFLOPS, 4),
-                                "flops_per_launch": int(flops),
-                                "flops_per_px_iteration": {"f32": OF_FLOW_F32_FLOPS_PER_PX,
-                                                           "f64": OF_FLOW_F64_FLOPS_PER_PX},
-                                "traffic": traffic, "frames_per_launch": hbm["frames_per_launch"],
-                                "avg_launch_us": hbm["avg_launch_us"], "launches_timed": kn,
-                                "timed_with": "feed 0 alone",
-                                "hbm": {"achieved": hbm["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                        "frac": hbm["frac"], "copy": hbm.get("copy"),
-                                        "algorithmic_bytes_per_launch": hbm["algorithmic_bytes_per_launch"]}}
+        if args.full:
+            avg_ms = kms / max(kn, 1)
+            if of:   # kn counts level-0 flow launches (iterations per batch)
+                kname = kkernel   # the level-0 kernel the library launched (dvc_of_ktime_kernel)
+                per_launch_frames = kframes * 2 / max(kn, 1)
+                bytes_per_launch = OF_FLOW_BYTES_PER_PX * W * H * per_launch_frames
+                traffic = pmc_traffic(os.path.join(ROOT, "profiles", "pmc_summary_of.json"), kname, workload,
+                                      per_launch_frames)
+            else:
+                kname = kkernel
+                per_launch_frames = kframes / max(kn, 1)
+                # I420 outputs: 1.5 B/px each instead of 3; 4:2:0 input surfaces are read
+                # in place (1.5 B/px instead of the BGR frame's 3)
+                back = BACK_BYTES_PER_PX_FRAME - (3.0 if args.out_format == "I420" else 0.0) - (1.5 if yuv else 0.0)
+                per_launch = FRONT_FUSED_BYTES_PER_PX_LAUNCH if kname == "k_front_fused" else BACK_BYTES_PER_PX_LAUNCH
+                bytes_per_launch = (back * kframes + per_launch * kn) * W * H / max(kn, 1)
+                traffic = pmc_traffic(os.path.join(ROOT, "profiles", "pmc_summary.json"),
+                                      "k_front" if kname == "k_front_fused" else "k_out", workload, per_launch_frames)
+            achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9
+            line["roofline"] = {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                                "traffic": traffic, "algorithmic_bytes_per_launch": int(bytes_per_launch),
+                                "frames_per_launch": round(per_launch_frames, 2),
+                                "avg_launch_us": round(avg_ms * 1e3, 2), "launches_timed": kn,
+                                "timed_with": "feed 0 alone"}
+            line["timing"]["ktime_pass"] = {"steps": ksteps, "launches": kn}
+            if traffic is not None:
+                line["roofline"]["traffic_source"] = (
+                    "committed rocprofv3 PMC profile of the same workload and launch size (2 x FETCH_SIZE + "
+                    "WRITE_SIZE, tools/profile_round.sh): profiles/" + ("pmc_summary_of.json" if of else "pmc_summary.json"))
+            # the same kernel's bytes (and the pipeline's) against this box's measured copy rate
+            cp_gbs, cp_detail = copy_bandwidth(local)
+            line["roofline"]["copy"] = {"GBps": round(cp_gbs, 1), "frac": round(achieved / cp_gbs, 4),
+                                        "pipeline_frac": round(line["config"]["pipeline_GBps_per_gpu"] / cp_gbs, 4),
+                                        "kernel": "dvc_copy_rate: hand-written 16 B/lane copy of 2 GiB", **cp_detail}
+            if of:   # k_flow's binding axis is the VALU (serial f64 recurrences), not HBM
+                px_it = W * H * per_launch_frames
+                flops = px_it * (OF_FLOW_F32_FLOPS_PER_PX + 2 * OF_FLOW_F64_FLOPS_PER_PX)
+                tf = flops / (avg_ms * 1e-3) / 1e12
+                hbm = line["roofline"]
+                line["roofline"] = {"bound": "valu", "kernel": kname, "achieved": round(tf, 3),
+                                    "peak": FP32_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s (FP32-equivalent)",
+                                    "frac": round(tf / FP32_VECTOR_PEAK_TFLOPS, 4),
+                                    "flops_per_launch": int(flops),
+                                    "flops_per_px_iteration": {"f32": OF_FLOW_F32_FLOPS_PER_PX,
+                                                               "f64": OF_FLOW_F64_FLOPS_PER_PX},
+                                    "traffic": traffic, "frames_per_launch": hbm["frames_per_launch"],
+                                    "avg_launch_us": hbm["avg_launch_us"], "launches_timed": kn,
+                                    "timed_with": "feed 0 alone",
+                                    "hbm": {"achieved": hbm["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                            "frac": hbm["frac"], "copy": hbm.get("copy"),
+                                            "algorithmic_bytes_per_launch": hbm["algorithmic_bytes_per_launch"]}}
         if cpu_base is not None:
             line["cpu_baseline"] = cpu_base
         print(json.dumps(line), flush=True)

@@ -16,9 +16,9 @@ for v in "${vars[@]}"; do
   mkdir -p $OUT
   echo "$v" > $OUT/env.txt
   env $v timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o f --output-format csv -- \
-      python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 "$@" > $OUT/fetch.log 2>&1
+      python3 bench.py --full --no-cpu-baseline --steps 2 --warmup 1 "$@" > $OUT/fetch.log 2>&1
   env $v timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d $OUT/write -o w --output-format csv -- \
-      python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 "$@" > $OUT/write.log 2>&1
+      python3 bench.py --full --no-cpu-baseline --steps 2 --warmup 1 "$@" > $OUT/write.log 2>&1
   FPL=$(python3 -c "import json; print(json.loads([l for l in open('$OUT/fetch.log') if l.startswith('{\"metric\"')][-1])['roofline']['frames_per_launch'])")
   python3 tools/pmc_summary.py $OUT/fetch/f_counter_collection.csv $OUT/write/w_counter_collection.csv \
       $OUT/pmc_summary.json "ab" "$FPL" > /dev/null

@@ -3,8 +3,9 @@
 # measured copy rate beside the roofline.
 set -e
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out/nc
-timeout -k 10 300 python3 -u bench.py > gpurun_out/nc/fd.json
-timeout -k 10 300 python3 -u bench.py --noisy > gpurun_out/nc/fd_noisy.json
-timeout -k 10 300 python3 -u bench.py --width 3840 --height 2160 > gpurun_out/nc/fd_4k.json
-timeout -k 10 300 python3 -u bench.py --path of > gpurun_out/nc/of.json
+O=${DVC_OUT:-bench_out}/nc   # where the lines go
+mkdir -p $O
+timeout -k 10 300 python3 -u bench.py --full > $O/fd.json
+timeout -k 10 300 python3 -u bench.py --full --noisy > $O/fd_noisy.json
+timeout -k 10 300 python3 -u bench.py --full --width 3840 --height 2160 > $O/fd_4k.json
+timeout -k 10 300 python3 -u bench.py --full --path of > $O/of.json

@@ -4,9 +4,10 @@
 # same workload (tools/profile_round.sh), and the OF bench line.
 set -e
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+O=${DVC_OUT:-bench_out}   # where the lines go
+mkdir -p $O
 TAG=${1:-r4}
-timeout -k 10 400 python3 bench.py > gpurun_out/${TAG}_bench_fd_1080p.json 2> gpurun_out/${TAG}_bench_fd.err
+timeout -k 10 400 python3 bench.py --full > $O/${TAG}_bench_fd_1080p.json 2> $O/${TAG}_bench_fd.err
 tools/profile_round.sh ${TAG}fd fd_1080p_single_feed_per_gpu
-timeout -k 10 300 python3 bench.py --path of --no-cpu-baseline --ktime-seconds 2 > gpurun_out/${TAG}_bench_of_1080p.json 2> gpurun_out/${TAG}_bench_of.err
-cat gpurun_out/${TAG}_bench_fd_1080p.json gpurun_out/${TAG}_bench_of_1080p.json
+timeout -k 10 300 python3 bench.py --full --path of --no-cpu-baseline --ktime-seconds 2 > $O/${TAG}_bench_of_1080p.json 2> $O/${TAG}_bench_of.err
+cat $O/${TAG}_bench_fd_1080p.json $O/${TAG}_bench_of_1080p.json

@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 TAG=${1:-r4}
 O=gpurun_out/$TAG
 mkdir -p $O
-b() { local name=$1; shift; timeout -k 10 400 python3 -u bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; tail -c 300 $O/bench_$name.json; echo; }
+b() { local name=$1; shift; timeout -k 10 400 python3 -u bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; tail -c 300 $O/bench_$name.json; echo; }
 # profiles first: the bench lines' `traffic` reads profiles/pmc_summary*.json
 bash tools/profile_round.sh ${TAG}fd fd_1080p_single_feed_per_gpu
 bash tools/profile_round.sh ${TAG}of of_1080p_single_feed_per_gpu --path of

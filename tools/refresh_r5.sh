@@ -12,7 +12,7 @@ cd "$(dirname "$0")/.."
 TAG=${1:-r5}
 O=gpurun_out/$TAG
 mkdir -p $O
-b() { local name=$1; shift; timeout -k 10 400 python3 -u bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; python3 -c "import json; d=json.load(open('$O/bench_$name.json')); print('$name', d['value'], d['ms_per_step'])"; }
+b() { local name=$1; shift; timeout -k 10 400 python3 -u bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; python3 -c "import json; d=json.load(open('$O/bench_$name.json')); print('$name', d['value'], d['ms_per_step'])"; }
 # profiles first: the bench lines' `traffic` reads profiles/pmc_summary*.json
 bash tools/profile_round.sh ${TAG}fd fd_1080p_single_feed_per_gpu
 bash tools/profile_round.sh ${TAG}of of_1080p_single_feed_per_gpu --path of

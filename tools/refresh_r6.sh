@@ -18,7 +18,7 @@ PART=${1:-a}
 O=gpurun_out/r6
 mkdir -p $O
 export TMPDIR=/tmp
-b() { local name=$1; shift; timeout -k 10 400 python3 -u bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err; python3 -c "import json; d=json.load(open('$O/bench_$name.json')); print('$name', d['value'], d['ms_per_step'])"; }
+b() { local name=$1; shift; timeout -k 10 400 python3 -u bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err; python3 -c "import json; d=json.load(open('$O/bench_$name.json')); print('$name', d['value'], d['ms_per_step'])"; }
 if [ "$PART" = a ]; then
   bash tools/profile_round.sh r6fd fd_1080p_single_feed_per_gpu
   bash tools/profile_round.sh r6of of_1080p_single_feed_per_gpu --path of
