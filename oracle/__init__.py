@@ -10,8 +10,14 @@ it and has no CPU fallback.
 
 Parity status: the oracle's numpy-side orchestration is pinned by golden
 vectors captured from the unmodified reference code (``tests/golden/``); its
-OpenCV primitives are restated from OpenCV 4.11's published algorithms and are
-"OCV-unverified" (cv2 is absent from this image) — see DESIGN.md §Parity.
+OpenCV primitives are restated from OpenCV 4.11's published algorithms. The
+frame-differencing ones are checked against scipy and known answers
+(``tests/test_oracle.py``). The optical-flow ones — pyramid blur and resize,
+polynomial expansion, update matrices, box solve, final flow, ellipse element,
+close/open, rectangles, vote threshold, 8x8 three-channel compression — are
+pinned to an independent float64 formulation (``tests/farneback_ref.py``,
+checked by ``tests/test_of_oracle.py``). Agreement with cv2's binary itself is
+still unverified, because cv2 is absent here — see DESIGN.md §Parity.
 """
 from __future__ import annotations
 

@@ -23,7 +23,15 @@
  * double sums (DVC_FLAG_OF_DIRECT_SUMS, oc_update_flow_box), and every float
  * expression is evaluated without contraction (-ffp-contract=off). The HIP
  * kernels implement both orders the same way, so each pair agrees to the last
- * bit; agreement with cv2 itself is "OCV-unverified" (no cv2 here).
+ * bit.
+ *
+ * Second opinion: tests/test_of_oracle.py holds this file to an independent
+ * float64 formulation (tests/farneback_ref.py, NumPy / scipy, no code shared)
+ * stage by stage — pyramid blur and resize, polynomial expansion, update
+ * matrices with the border scale, the box solve in both orders, the final
+ * flow, the ellipse element, close/open, rectangles, the vote threshold and
+ * the 8x8 three-channel compression. Agreement with cv2's binary itself is
+ * still unverified (no cv2 here).
  */
 #include <float.h>
 #include <math.h>
