@@ -16,8 +16,10 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdvc_hip.so")
-SOURCES = ["fd_kernels.hip", "fd_api.hip", "of_kernels.hip", "of_api.hip", "yuv_kernels.hip", "diag.hip"]
-HEADERS = ["fd_kernels.h", "dvc_device.h", "of_kernels.h", "host_common.h", "yuv_kernels.h", "yuv_px.h"]
+SOURCES = ["fd_kernels.hip", "fd_api.hip", "of_kernels.hip", "of_api.hip", "yuv_kernels.hip", "diag.hip",
+           "jpeg_kernels.hip", "jpeg_api.hip"]
+HEADERS = ["fd_kernels.h", "dvc_device.h", "of_kernels.h", "host_common.h", "yuv_kernels.h", "yuv_px.h",
+           "jpeg_kernels.h", "jpeg_tables.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 DVC_OK = 0
@@ -33,6 +35,7 @@ DVC_FLAG_FD_UNFUSED = 0x40
 KTIME_OUT, KTIME_FRONT_FUSED = 0, 1         # dvc_fd_ktime_kernel: which kernel KTIMING timed
 KTIME_FLOW, KTIME_FLOW_SCAN, KTIME_FLOW_SCAN2 = 2, 3, 4   # dvc_of_ktime_kernel: the level-0 flow kernel
 FMT_BGR, FMT_I420, FMT_NV12 = 0, 1, 2      # DVC_FMT_* frame formats (video I/O)
+FMT_GRAY = 3                               # DVC_FMT_GRAY: one channel (the JPEG encoder's mask videos)
 FORMATS = {"BGR": FMT_BGR, "I420": FMT_I420, "NV12": FMT_NV12}
 
 PLANE_GRAY, PLANE_MOTION, PLANE_FILTERED, PLANE_ACC, PLANE_DILATED = range(5)
@@ -48,9 +51,10 @@ EXPORTS = [
     "dvc_of_debug_read", "dvc_host_alloc", "dvc_host_free", "dvc_yuv420_to_bgr", "dvc_bgr_to_i420",
     "dvc_copy_rate", "dvc_ofc_create", "dvc_ofc_run", "dvc_ofc_sync", "dvc_ofc_destroy",
     "dvc_fd_set_state", "dvc_of_set_state", "dvc_fd_ktime_kernel", "dvc_of_ktime_kernel",
-    "dvc_fd_graph_stats",
+    "dvc_fd_graph_stats", "dvc_jpeg_create", "dvc_jpeg_destroy", "dvc_jpeg_header", "dvc_jpeg_bound",
+    "dvc_jpeg_encode", "dvc_jpeg_sync",
 ]
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_BATCH = 512
 
 
@@ -232,6 +236,16 @@ def lib() -> ctypes.CDLL:
                                 ctypes.POINTER(ctypes.c_double)]
     L.dvc_copy_rate.restype = ctypes.c_int
     L.dvc_yuv420_to_bgr.restype = ctypes.c_int
+    L.dvc_jpeg_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                  vp, ctypes.c_uint32, ctypes.POINTER(vp)]
+    L.dvc_jpeg_destroy.argtypes = [vp]
+    L.dvc_jpeg_destroy.restype = None
+    L.dvc_jpeg_header.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    L.dvc_jpeg_bound.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
+    L.dvc_jpeg_encode.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t, vp]
+    L.dvc_jpeg_sync.argtypes = [vp]
+    for name in ("dvc_jpeg_create", "dvc_jpeg_header", "dvc_jpeg_bound", "dvc_jpeg_encode", "dvc_jpeg_sync"):
+        getattr(L, name).restype = ctypes.c_int
     L.dvc_bgr_to_i420.restype = ctypes.c_int
     for name in ("dvc_of_create", "dvc_of_prime", "dvc_of_step", "dvc_of_step_batch", "dvc_of_sync",
                  "dvc_of_get_stats", "dvc_of_read_plane", "dvc_of_read_flow", "dvc_of_ktime", "dvc_of_compress"):
@@ -383,6 +397,71 @@ def bgr_to_i420(frames, device: int = 0):
     check(lib().dvc_bgr_to_i420(f.ctypes.data, 3 * W, 3 * W * H, W, H, n, out.ctypes.data, W, 0, out[0].nbytes,
                                 int(device), None, 0))
     return out[0] if one else out
+
+
+class JpegEncoder:
+    """cv2.VideoWriter's codec end on the GPU (dvc_jpeg): host numpy frames,
+    (n, H, W, 3) BGR or (n, H, W) single-channel, -> one ``bytes`` per frame, the
+    frame's JFIF entropy data and EOI; ``header`` (SOI..SOS, constant per
+    encoder) in front of it makes a complete baseline JPEG image."""
+
+    def __init__(self, width: int, height: int, is_color: bool = True, quality: int = 75, max_batch: int = 8,
+                 device: int = 0):
+        self.W, self.H, self.is_color = int(width), int(height), bool(is_color)
+        self.fmt = FMT_BGR if is_color else FMT_GRAY
+        self._h = self._out = None
+        h = ctypes.c_void_p()
+        check(lib().dvc_jpeg_create(self.W, self.H, self.fmt, int(quality), max(1, int(max_batch)), int(device), None,
+                                    0, ctypes.byref(h)))
+        self._h = h
+        n = ctypes.c_size_t()
+        check(lib().dvc_jpeg_header(h, None, 0, ctypes.byref(n)))
+        buf = (ctypes.c_uint8 * n.value)()
+        check(lib().dvc_jpeg_header(h, buf, n.value, ctypes.byref(n)))
+        self.header = bytes(buf)
+        check(lib().dvc_jpeg_bound(self.W, self.H, self.fmt, ctypes.byref(n)))
+        self.bound = int(n.value)
+
+    @staticmethod
+    def alloc(shape):
+        """Page-locked frames for :meth:`encode` (DMA'd directly, no staging copy)."""
+        return pinned(shape)
+
+    def encode(self, frames) -> list:
+        import numpy as np
+        f = np.ascontiguousarray(frames, dtype=np.uint8)
+        shape = (self.H, self.W, 3) if self.is_color else (self.H, self.W)
+        if f.shape == shape:
+            f = f[None]
+        if f.shape[1:] != shape:
+            raise ValueError(f"frames {f.shape} do not match {shape}")
+        n = f.shape[0]
+        if n == 0:
+            return []
+        row = f[0][0].nbytes
+        sizes = np.zeros(n, np.uint32)
+        # slots of the raw frame size almost always fit; the worst case is several times that
+        for stride in (min(self.bound, max(4096, f[0].nbytes)), self.bound):
+            if self._out is None or self._out.shape[0] < n or self._out.shape[1] != stride:
+                self._out = pinned((n, stride))   # kept for the next call
+            out = self._out
+            rc = lib().dvc_jpeg_encode(self._h, f.ctypes.data, row, f[0].nbytes, n, out.ctypes.data, stride,
+                                       sizes.ctypes.data)
+            if rc != DVC_E_NOMEM or stride == self.bound:
+                check(rc)
+                break
+        return [out[i, :int(sizes[i])].tobytes() for i in range(n)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dvc_jpeg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def copy_rate(device: int = 0, nbytes: int = 1 << 30, reps: int = 20, nontemporal: bool = True) -> float:

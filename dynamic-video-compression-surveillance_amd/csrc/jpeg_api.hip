@@ -1,0 +1,317 @@
+// jpeg_api.hip — C-ABI of the Motion-JPEG encoder (include/dvc.h, dvc_jpeg_*):
+// what the reference's cv2.VideoWriter does with every written frame
+// (frame_differencing.py:63-65,112,131; motion_compression_opt.py:50-52,99-100,
+// 135-136,185), as baseline JPEG instead of MPEG-4 Part 2. The stream format is
+// DESIGN.md "Motion-JPEG stream"; the kernels are in jpeg_kernels.hip.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/dvc.h"
+#include "host_common.h"
+#include "jpeg_kernels.h"
+#include "jpeg_tables.h"
+
+using dvc_host::fail;
+
+namespace {
+
+// Worst-case bytes of one restart segment of `bps` blocks: every byte stuffed.
+uint64_t seg_cap(uint64_t bps) { return 2 * ((bps * dvc::kJpegMaxBlockBits + 7) / 8); }
+
+bool geometry(int width, int height, int fmt, dvc::JpegGeom* g)
+{
+    if (width < 1 || height < 1 || width > 65520 || height > 65520) return false;
+    if (fmt != DVC_FMT_BGR && fmt != DVC_FMT_GRAY) return false;
+    const int gray = fmt == DVC_FMT_GRAY, m = gray ? 8 : 16;
+    g->W = width;
+    g->H = height;
+    g->gray = gray;
+    g->mcus_x = (width + m - 1) / m;
+    g->nseg = (height + m - 1) / m;
+    g->bps = g->mcus_x * (gray ? 1 : 6);
+    g->units_x = gray ? (g->mcus_x + 3) / 4 : g->mcus_x;
+    g->segcap = (uint32_t)seg_cap((uint64_t)g->bps);
+    return true;
+}
+
+// Worst-case entropy bytes of a frame: its segments, their RST markers, EOI.
+uint64_t frame_bound(const dvc::JpegGeom& g) { return (uint64_t)g.nseg * ((uint64_t)g.segcap + 2); }
+
+void quant_table(const uint8_t* base, int quality, uint16_t* q)
+{
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int i = 0; i < 64; ++i) q[i] = (uint16_t)std::min(255, std::max(1, (base[i] * s + 50) / 100));
+}
+
+// Canonical codes from a DHT's BITS / HUFFVAL, as a decoder derives them.
+void canonical(const uint8_t* bits, const uint8_t* vals, uint32_t* table)
+{
+    uint32_t code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < bits[len - 1]; ++i, ++k, ++code) table[vals[k]] = (uint32_t)len << 16 | code;
+        code <<= 1;
+    }
+}
+
+void fill_tables(int quality, dvc::JpegTables* t)
+{
+    using namespace dvc_jpeg_tab;
+    std::memset(t, 0, sizeof(*t));
+    quant_table(kBaseLuma, quality, t->q[0]);
+    quant_table(kBaseChroma, quality, t->q[1]);
+    canonical(kDcBits, kDcVals, t->dc);
+    canonical(kAcBits, kAcVals, t->ac);
+    for (int k = 0; k < 64; ++k) t->zpos[kZigzag[k]] = (uint8_t)k;
+}
+
+void put16(std::vector<uint8_t>& v, unsigned x)
+{
+    v.push_back((uint8_t)(x >> 8));
+    v.push_back((uint8_t)x);
+}
+
+// SOI, APP0 JFIF, 2 x DQT, SOF0, 2 x DHT, DRI, SOS header.
+std::vector<uint8_t> make_header(const dvc::JpegGeom& g, const dvc::JpegTables& t)
+{
+    using namespace dvc_jpeg_tab;
+    std::vector<uint8_t> v = {0xff, 0xd8, 0xff, 0xe0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    for (int id = 0; id < 2; ++id) {
+        v.insert(v.end(), {0xff, 0xdb, 0, 67, (uint8_t)id});
+        for (int k = 0; k < 64; ++k) v.push_back((uint8_t)t.q[id][kZigzag[k]]);
+    }
+    const int nc = g.gray ? 1 : 3;
+    v.insert(v.end(), {0xff, 0xc0});
+    put16(v, 8 + 3 * nc);
+    v.push_back(8);
+    put16(v, g.H);
+    put16(v, g.W);
+    v.push_back((uint8_t)nc);
+    for (int c = 0; c < nc; ++c) v.insert(v.end(), {(uint8_t)(c + 1), (uint8_t)(c == 0 && !g.gray ? 0x22 : 0x11), (uint8_t)(c ? 1 : 0)});
+    const struct {
+        uint8_t id;
+        const uint8_t *bits, *vals;
+        int n;
+    } dht[2] = {{0x00, kDcBits, kDcVals, 12}, {0x10, kAcBits, kAcVals, 162}};
+    for (const auto& d : dht) {
+        v.insert(v.end(), {0xff, 0xc4});
+        put16(v, 2 + 1 + 16 + d.n);
+        v.push_back(d.id);
+        v.insert(v.end(), d.bits, d.bits + 16);
+        v.insert(v.end(), d.vals, d.vals + d.n);
+    }
+    v.insert(v.end(), {0xff, 0xdd, 0, 4});
+    put16(v, g.mcus_x);
+    v.insert(v.end(), {0xff, 0xda});
+    put16(v, 6 + 2 * nc);
+    v.push_back((uint8_t)nc);
+    for (int c = 0; c < nc; ++c) v.insert(v.end(), {(uint8_t)(c + 1), 0x00});
+    v.insert(v.end(), {0, 63, 0});
+    return v;
+}
+
+}  // namespace
+
+struct dvc_jpeg {
+    dvc::JpegGeom g{};
+    dvc::JpegTables tab{};
+    std::vector<uint8_t> header;
+    int device = -1, max_batch = 1, chan = 3;
+    uint32_t flags = 0;
+    uint64_t bound = 0;
+    hipStream_t stream = nullptr;   // the caller's (may be NULL = legacy default) or our own
+    bool own_stream = false;
+    dvc::JpegTables* d_tab = nullptr;
+    dvc::JpegBufs b{};
+    // host-pointer mode: staged frames (rows of ip bytes), output slots, sizes
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    uint32_t* d_sizes = nullptr;
+    size_t ip = 0;
+};
+
+static void jpeg_free(dvc_jpeg* h)
+{
+    for (void* p : {(void*)h->d_tab, (void*)h->b.levels, (void*)h->b.boff, (void*)h->b.segbits, (void*)h->b.seglen,
+                    (void*)h->b.scratch, (void*)h->b.overflow, (void*)h->d_in, (void*)h->d_out, (void*)h->d_sizes})
+        if (p) (void)hipFree(p);
+    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+}
+
+extern "C" {
+
+int dvc_jpeg_bound(int width, int height, int fmt, size_t* bytes)
+{
+    dvc::JpegGeom g{};
+    if (!bytes) return fail(DVC_E_INVALID, "NULL argument");
+    if (!geometry(width, height, fmt, &g)) return fail(DVC_E_INVALID, "frame %dx%d format %d invalid", width, height, fmt);
+    *bytes = (size_t)frame_bound(g);
+    return DVC_OK;
+}
+
+int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, int device, void* hip_stream,
+                    uint32_t flags, dvc_jpeg** out)
+{
+    if (!out) return fail(DVC_E_INVALID, "NULL argument");
+    if (fmt == DVC_FMT_I420 || fmt == DVC_FMT_NV12)
+        return fail(DVC_E_UNSUPPORTED, "the encoder takes DVC_FMT_BGR or DVC_FMT_GRAY frames (JFIF is full-range)");
+    dvc::JpegGeom g{};
+    if (!geometry(width, height, fmt, &g)) return fail(DVC_E_INVALID, "frame %dx%d format %d invalid", width, height, fmt);
+    if (quality < 1 || quality > 100) return fail(DVC_E_INVALID, "quality %d outside 1..100", quality);
+    if (max_batch < 0 || max_batch > DVC_MAX_BATCH) return fail(DVC_E_INVALID, "max_batch %d outside 1..%d", max_batch,
+                                                                DVC_MAX_BATCH);
+    if (frame_bound(g) > 0x7fffffffull) return fail(DVC_E_UNSUPPORTED, "frame %dx%d too large", width, height);
+    dvc_jpeg* h = new dvc_jpeg();
+    h->g = g;
+    h->device = device;
+    h->max_batch = max_batch ? max_batch : 1;
+    h->flags = flags;
+    h->chan = g.gray ? 1 : 3;
+    h->bound = frame_bound(g);
+    fill_tables(quality, &h->tab);
+    h->header = make_header(g, h->tab);
+    *out = h;
+    if (device < 0) return DVC_OK;   // host-only handle: dvc_jpeg_header alone
+    *out = nullptr;
+    hipError_t e = hipSetDevice(device);
+    const size_t mb = h->max_batch, nblk = (size_t)g.nseg * g.bps, nseg = g.nseg;
+    h->ip = ((size_t)h->chan * g.W + 3) & ~(size_t)3;
+    if (e == hipSuccess) {
+        if (hip_stream || (flags & DVC_FLAG_JOIN_STREAM)) {
+            h->stream = (hipStream_t)hip_stream;
+        } else {
+            e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+            h->own_stream = e == hipSuccess;
+        }
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_tab, sizeof(dvc::JpegTables));
+    if (e == hipSuccess) e = hipMemcpy(h->d_tab, &h->tab, sizeof(dvc::JpegTables), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b.levels, mb * nblk * 64 * sizeof(int16_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b.boff, mb * nblk * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b.segbits, mb * nseg * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b.seglen, mb * nseg * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b.scratch, mb * nseg * (size_t)g.segcap);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->b.overflow, sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(h->b.overflow, 0, sizeof(uint32_t));
+    if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
+        e = hipMalloc((void**)&h->d_in, mb * h->ip * g.H);   // staged frames
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_out, mb * (size_t)h->bound);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_sizes, mb * sizeof(uint32_t));
+    }
+    if (e != hipSuccess) {
+        jpeg_free(h);
+        delete h;
+        return fail(e == hipErrorOutOfMemory ? DVC_E_NOMEM : DVC_E_HIP, "jpeg create: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return DVC_OK;
+}
+
+int dvc_jpeg_header(const dvc_jpeg* h, uint8_t* dst, size_t cap, size_t* n)
+{
+    if (!h || !n) return fail(DVC_E_INVALID, "NULL argument");
+    *n = h->header.size();
+    if (!dst) return DVC_OK;   // size query
+    if (cap < h->header.size()) return fail(DVC_E_NOMEM, "header needs %zu bytes, %zu given", h->header.size(), cap);
+    std::memcpy(dst, h->header.data(), h->header.size());
+    return DVC_OK;
+}
+
+int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t frame_stride, int n, uint8_t* out,
+                    size_t out_stride, uint32_t* sizes)
+{
+    if (!h || !frames || !out || !sizes) return fail(DVC_E_INVALID, "NULL argument");
+    if (h->device < 0) return fail(DVC_E_STATE, "a host-only handle cannot encode");
+    if (n < 0) return fail(DVC_E_INVALID, "negative frame count");
+    const dvc::JpegGeom& g = h->g;
+    const size_t roww = (size_t)h->chan * g.W, H = g.H;
+    if (pitch < roww) return fail(DVC_E_INVALID, "pitch invalid");
+    if (n > 1 && frame_stride < pitch * (H - 1) + roww) return fail(DVC_E_INVALID, "frame stride invalid");
+    HIP_OK(hipSetDevice(h->device));
+    const bool devp = h->flags & DVC_FLAG_DEVICE_PTRS;
+    hipStream_t st = h->stream;
+    bool overflow = false;
+    std::vector<uint32_t> hs((size_t)h->max_batch);
+    for (int f0 = 0; f0 < n; f0 += h->max_batch) {
+        const int m = std::min(h->max_batch, n - f0);
+        const uint8_t* in = frames + (size_t)f0 * frame_stride;
+        uint8_t* o = out + (size_t)f0 * out_stride;
+        const uint8_t* kd = in;
+        size_t kp = pitch, kfs = frame_stride;
+        if (!devp) {   // frames up, rows of ip bytes: packed frames in one copy each (a 2-D copy of
+                       // pageable memory goes row by row), a packed batch in one
+            const bool packed = pitch == roww && roww == h->ip;
+            if (packed && (m == 1 || frame_stride == roww * H)) {
+                HIP_OK(hipMemcpyAsync(h->d_in, in, (size_t)m * roww * H, hipMemcpyHostToDevice, st));
+            } else {
+                for (int t = 0; t < m; ++t) {
+                    const uint8_t* src = in + (size_t)t * frame_stride;
+                    if (packed)
+                        HIP_OK(hipMemcpyAsync(h->d_in + t * roww * H, src, roww * H, hipMemcpyHostToDevice, st));
+                    else
+                        HIP_OK(hipMemcpy2DAsync(h->d_in + t * h->ip * H, h->ip, src, pitch, roww, H,
+                                                hipMemcpyHostToDevice, st));
+                }
+            }
+            kd = h->d_in;
+            kp = h->ip;
+            kfs = h->ip * H;
+        }
+        HIP_OK(dvc::jpeg_launch_dct(kd, kp, kfs, m, g, h->d_tab, h->b, st));
+        HIP_OK(dvc::jpeg_launch_bits(m, g, h->d_tab, h->b, st));
+        HIP_OK(dvc::jpeg_launch_pack(m, g, h->d_tab, h->b, st));
+        if (devp) {
+            HIP_OK(dvc::jpeg_launch_gather(m, g, h->b, o, out_stride, sizes + f0, st));
+            continue;
+        }
+        const size_t slot = (size_t)std::min<uint64_t>(out_stride, h->bound);
+        uint32_t hov = 0;
+        HIP_OK(dvc::jpeg_launch_gather(m, g, h->b, h->d_out, slot, h->d_sizes, st));
+        HIP_OK(hipMemcpyAsync(hs.data(), h->d_sizes, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(&hov, h->b.overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (hov) {
+            overflow = true;
+            HIP_OK(hipMemsetAsync(h->b.overflow, 0, sizeof(uint32_t), st));
+        }
+        for (int t = 0; t < m; ++t) {
+            sizes[f0 + t] = hs[t];
+            if (hs[t] <= slot)
+                HIP_OK(hipMemcpyAsync(o + (size_t)t * out_stride, h->d_out + t * slot, hs[t], hipMemcpyDeviceToHost, st));
+        }
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    if (overflow) return fail(DVC_E_NOMEM, "a frame's entropy data exceeds out_stride %zu (sizes hold the needed lengths)",
+                              out_stride);
+    return DVC_OK;
+}
+
+int dvc_jpeg_sync(dvc_jpeg* h)
+{
+    if (!h) return fail(DVC_E_INVALID, "NULL handle");
+    if (h->device < 0) return DVC_OK;
+    HIP_OK(hipSetDevice(h->device));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    if (h->flags & DVC_FLAG_DEVICE_PTRS) {   // an overflow of an asynchronous call is reported here
+        uint32_t hov = 0;
+        HIP_OK(hipMemcpy(&hov, h->b.overflow, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (hov) {
+            HIP_OK(hipMemset(h->b.overflow, 0, sizeof(uint32_t)));
+            return fail(DVC_E_NOMEM, "a frame's entropy data exceeded its output slot (sizes hold the needed lengths)");
+        }
+    }
+    return DVC_OK;
+}
+
+void dvc_jpeg_destroy(dvc_jpeg* h)
+{
+    if (!h) return;
+    if (h->device >= 0) {
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        jpeg_free(h);
+    }
+    delete h;
+}
+
+}  // extern "C"

@@ -1,0 +1,57 @@
+// jpeg_kernels.h — baseline-JPEG encoder kernels (DESIGN.md "Motion-JPEG
+// stream"). Internal launch interface; the C-ABI is in include/dvc.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace dvc {
+
+// The most bits one block can take: a DC code (16 + 11 magnitude bits) and 63
+// AC codes (16 + 10 each). Runs >= 16 cost less than the coefficients they skip.
+constexpr int kJpegMaxBlockBits = 27 + 63 * 26;
+// Blocks whose codes k_jpeg_pack assembles in LDS at a time.
+constexpr int kJpegChunk = 64;
+
+// Per-handle tables in device memory.
+struct JpegTables {
+    uint16_t q[2][64];   // quantiser, natural order: luma, chroma
+    uint32_t dc[12];     // code length << 16 | code, by DC size
+    uint32_t ac[256];    // the same by (run << 4 | size); 0x00 EOB, 0xF0 ZRL
+    uint8_t zpos[64];    // zigzag position of natural index i
+};
+
+// One frame's geometry. A restart segment is one MCU row: `bps` blocks in scan
+// order (colour: Y00 Y01 Y10 Y11 Cb Cr per 16x16 MCU; gray: one 8x8 block per MCU).
+struct JpegGeom {
+    int W, H;
+    int gray;       // 1: DVC_FMT_GRAY
+    int mcus_x;     // MCUs per segment
+    int nseg;       // segments (MCU rows) per frame
+    int bps;        // blocks per segment
+    int units_x;    // k_jpeg_dct work units per MCU row (colour: one MCU; gray: four blocks)
+    uint32_t segcap;   // bytes of one segment's scratch slot (its worst case, stuffing included)
+};
+
+// Work buffers for max_batch frames (frame f's part at index f * per-frame count).
+struct JpegBufs {
+    int16_t* levels;     // nseg * bps * 64 quantised levels, zigzag order, DC undifferenced
+    uint32_t* boff;      // nseg * bps: a block's bit offset inside its segment
+    uint32_t* segbits;   // nseg: a segment's bits
+    uint32_t* seglen;    // nseg: its bytes after stuffing
+    uint8_t* scratch;    // nseg * segcap
+    uint32_t* overflow;  // one word: set when a frame did not fit its output slot
+};
+
+// n frames (rows of `pitch` bytes, frames `fstride` apart; BGR or one channel)
+// -> levels.
+hipError_t jpeg_launch_dct(const uint8_t* frames, size_t pitch, size_t fstride, int n, const JpegGeom& g,
+                           const JpegTables* tab, const JpegBufs& b, hipStream_t st);
+// levels -> boff, segbits.
+hipError_t jpeg_launch_bits(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st);
+// levels, boff, segbits -> scratch, seglen.
+hipError_t jpeg_launch_pack(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st);
+// scratch, seglen -> out + f * out_stride (segments, RST markers, EOI), sizes[f].
+hipError_t jpeg_launch_gather(int n, const JpegGeom& g, const JpegBufs& b, uint8_t* out, size_t out_stride,
+                              uint32_t* sizes, hipStream_t st);
+
+}  // namespace dvc

@@ -1,0 +1,446 @@
+// jpeg_kernels.hip — baseline-JPEG encoder for gfx950 (wave64): the frames the
+// reference hands to cv2.VideoWriter.write (frame_differencing.py:112,131;
+// motion_compression_opt.py:99-100,185) become JFIF entropy data on the GPU.
+// DESIGN.md "Motion-JPEG stream" is the normative text of the arithmetic.
+//
+//   k_jpeg_dct     BGR / gray -> YCbCr, 4:2:0, integer DCT, quantise, zigzag
+//   k_jpeg_bits    per-block code lengths, bit offsets along each restart segment
+//   k_jpeg_pack    codes OR-ed into an LDS bit buffer, 0xFF stuffing -> scratch
+//   k_jpeg_gather  segments + RST markers + EOI -> the frame's output slot
+//
+// All four are integer-exact; every store is an ordinary vector store.
+#include "jpeg_kernels.h"
+
+namespace dvc {
+
+namespace {
+
+// M[k][n] = round(8192 * a(k) * cos((2n+1) k pi / 16)), n < 4 (M[k][7-n] = +-M[k][n])
+static __device__ const int kDctM[8][4] = {
+    {2896, 2896, 2896, 2896},  {4017, 3406, 2276, 799},   {3784, 1567, -1567, -3784}, {3406, -799, -4017, -2276},
+    {2896, -2896, -2896, 2896}, {2276, -4017, 799, 3406}, {1567, -3784, 3784, -1567}, {799, -2276, 3406, -4017}};
+
+// out[k] = (sum_n M[k][n] x[n] + rnd) >> sh: full integer sums, the even / odd
+// symmetry of M used (exact).
+__device__ __forceinline__ void dct8(const int x[8], int out[8], int rnd, int sh)
+{
+    int s[4], d[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        s[n] = x[n] + x[7 - n];
+        d[n] = x[n] - x[7 - n];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int* v = (k & 1) ? d : s;
+        int acc = rnd;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc += kDctM[k][n] * v[n];
+        out[k] = acc >> sh;
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// Exclusive prefix of v over the 256 threads; *total = their sum. s_w: 4 words.
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, uint32_t* total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t inc = wave_incl_scan(v, lane);
+    __syncthreads();   // the previous round's readers are done with s_w
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const uint32_t x = s_w[w];
+        if (w < wave) base += x;
+        tot += x;
+    }
+    *total = tot;
+    return base + inc - v;
+}
+
+// ---- k_jpeg_dct -------------------------------------------------------------------
+// 256 threads = 4 waves, one work unit each: a 16x16 MCU (colour, 6 blocks) or
+// four 8x8 blocks side by side (gray). A lane loads 4 pixels of one row (three
+// aligned dwords of BGR, or one of gray), clamped to the frame edge.
+template <bool GRAY>
+__global__ __launch_bounds__(256) void k_jpeg_dct(const uint8_t* __restrict__ frames, size_t pitch, size_t fstride,
+                                                  JpegGeom g, const JpegTables* __restrict__ tab,
+                                                  int16_t* __restrict__ levels, int aligned)
+{
+    constexpr int NB = GRAY ? 4 : 6;
+    constexpr int NPX = GRAY ? 256 : 768;
+    __shared__ int16_t s_px[4][NPX];        // gray: 8 rows x 32; colour: Y, Cb, Cr planes of 16 x 16
+    __shared__ int s_r[4][NB * 64];         // after the row pass
+    __shared__ int16_t s_lv[4][NB * 64];    // levels, zigzag order
+    __shared__ uint16_t s_q[128];
+    __shared__ uint8_t s_zpos[64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (threadIdx.x < 128) s_q[threadIdx.x] = (&tab->q[0][0])[threadIdx.x];
+    if (threadIdx.x < 64) s_zpos[threadIdx.x] = tab->zpos[threadIdx.x];
+    const int units = g.units_x * g.nseg;
+    int unit = blockIdx.x * 4 + wave;
+    const bool live = unit < units;
+    if (!live) unit = units - 1;
+    const int uy = unit / g.units_x, ux = unit - uy * g.units_x;
+    const uint8_t* f = frames + (size_t)blockIdx.y * fstride;
+    int16_t* px = s_px[wave];
+
+    if (GRAY) {
+        const int r = lane >> 3, run = lane & 7;
+        const int x0 = ux * 32 + run * 4, y = min(uy * 8 + r, g.H - 1);
+        const uint8_t* row = f + (size_t)y * pitch;
+        uint32_t v;
+        if (aligned && x0 + 4 <= g.W) {
+            v = *reinterpret_cast<const uint32_t*>(row + x0);
+        } else {
+            v = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v |= (uint32_t)row[min(x0 + i, g.W - 1)] << (8 * i);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) px[r * 32 + run * 4 + i] = (int16_t)((v >> (8 * i)) & 0xff);
+    } else {
+        const int r = lane >> 2, run = lane & 3;
+        const int x0 = ux * 16 + run * 4, y = min(uy * 16 + r, g.H - 1);
+        const uint8_t* row = f + (size_t)y * pitch;
+        uint8_t c[12];
+        if (aligned && x0 + 4 <= g.W) {
+            const uint32_t* p = reinterpret_cast<const uint32_t*>(row + 3 * (size_t)x0);
+#pragma unroll
+            for (int w = 0; w < 3; ++w) {
+                const uint32_t v = p[w];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) c[4 * w + i] = (uint8_t)(v >> (8 * i));
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint8_t* q = row + 3 * (size_t)min(x0 + i, g.W - 1);
+                c[3 * i] = q[0];
+                c[3 * i + 1] = q[1];
+                c[3 * i + 2] = q[2];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int B = c[3 * i], G = c[3 * i + 1], R = c[3 * i + 2];
+            const int o = r * 16 + run * 4 + i;
+            px[o] = (int16_t)((19595 * R + 38470 * G + 7471 * B + 32768) >> 16);
+            px[256 + o] = (int16_t)((-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16);
+            px[512 + o] = (int16_t)((32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16);
+        }
+    }
+    __syncthreads();
+
+    const int blk = lane >> 3, i8 = lane & 7;   // row pass: row i8 of block blk; column pass: its column i8
+    if (blk < NB) {
+        int x[8], o[8];
+        if (GRAY) {
+#pragma unroll
+            for (int n = 0; n < 8; ++n) x[n] = px[i8 * 32 + blk * 8 + n] - 128;
+        } else if (blk < 4) {
+            const int base = ((blk >> 1) * 8 + i8) * 16 + (blk & 1) * 8;
+#pragma unroll
+            for (int n = 0; n < 8; ++n) x[n] = px[base + n] - 128;
+        } else {
+            const int16_t* p = px + 256 * (blk - 3) + 2 * i8 * 16;
+#pragma unroll
+            for (int n = 0; n < 8; ++n) x[n] = ((p[2 * n] + p[2 * n + 1] + p[16 + 2 * n] + p[17 + 2 * n] + 2) >> 2) - 128;
+        }
+        dct8(x, o, 512, 10);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s_r[wave][blk * 64 + i8 * 8 + k] = o[k];
+    }
+    __syncthreads();
+    if (blk < NB) {
+        int x[8], o[8];
+#pragma unroll
+        for (int y = 0; y < 8; ++y) x[y] = s_r[wave][blk * 64 + y * 8 + i8];
+        dct8(x, o, 32768, 16);
+        const uint16_t* q = s_q + ((!GRAY && blk >= 4) ? 64 : 0);
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+            const int nat = v * 8 + i8;
+            const int Q = q[nat], F = o[v];
+            int l = (int)((uint32_t)(abs(F) + (Q >> 1)) / (uint32_t)Q);
+            if (nat) l = min(l, 1023);
+            s_lv[wave][blk * 64 + s_zpos[nat]] = (int16_t)(F < 0 ? -l : l);
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const size_t fblocks = (size_t)g.nseg * g.bps;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(s_lv[wave]);
+    if (GRAY) {
+        const int nv = min(4, g.mcus_x - ux * 4);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(levels + ((size_t)blockIdx.y * fblocks + (size_t)uy * g.bps + ux * 4) * 64);
+        for (int i = lane; i < nv * 32; i += 64) dst[i] = src[i];
+    } else {
+        uint32_t* dst = reinterpret_cast<uint32_t*>(levels + ((size_t)blockIdx.y * fblocks + (size_t)uy * g.bps + ux * 6) * 64);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) dst[lane + 64 * i] = src[lane + 64 * i];
+    }
+}
+
+// ---- entropy coding: what one lane (one zigzag coefficient) emits ---------------------
+struct LaneCode {
+    uint32_t code;   // Huffman code followed by the magnitude bits
+    int n;           // their length (<= 27)
+    int nzrl;        // ZRL codes in front (runs of 16 zeros)
+};
+
+__device__ __forceinline__ LaneCode lane_code(int lv, int lane, int pred, const uint32_t* s_dc, const uint32_t* s_ac)
+{
+    LaneCode c{0u, 0, 0};
+    const unsigned long long nz = __ballot(lv != 0 && lane > 0) | 1ull;   // bit 0: the DC ends no run
+    int val = lv, size;
+    uint32_t e;
+    if (lane == 0) {
+        val = max(-2047, min(2047, lv - pred));
+        size = 32 - __clz(abs(val));
+        e = s_dc[size];
+    } else if (lv != 0) {
+        const unsigned long long below = nz & ((1ull << lane) - 1ull);
+        const int run = lane - (63 - __clzll((long long)below)) - 1;
+        c.nzrl = run >> 4;
+        size = 32 - __clz(abs(val));
+        e = s_ac[((run & 15) << 4) | size];
+    } else if (lane == 63) {   // trailing zeros: EOB
+        e = s_ac[0];
+        c.code = e & 0xffffu;
+        c.n = (int)(e >> 16);
+        return c;
+    } else {
+        return c;
+    }
+    const uint32_t mag = (uint32_t)(val < 0 ? val - 1 : val) & ((1u << size) - 1u);
+    c.code = ((e & 0xffffu) << size) | mag;
+    c.n = (int)(e >> 16) + size;
+    return c;
+}
+
+// The DC predictor of block j of a segment: the previous block of its component.
+__device__ __forceinline__ int dc_pred(const int16_t* seg_levels, int j, int gray)
+{
+    int p;
+    if (gray) {
+        p = j - 1;
+    } else {
+        const int b = j % 6;
+        p = b == 0 ? j - 3 : (b < 4 ? j - 1 : j - 6);
+    }
+    return p >= 0 ? seg_levels[(size_t)p * 64] : 0;
+}
+
+// One workgroup per (segment, frame): a wave per block sizes its codes (a lane
+// per coefficient, the run from a ballot), then the block scans the lengths.
+__global__ __launch_bounds__(256) void k_jpeg_bits(JpegGeom g, const JpegTables* __restrict__ tab,
+                                                   const int16_t* __restrict__ levels, uint32_t* __restrict__ boff,
+                                                   uint32_t* __restrict__ segbits)
+{
+    __shared__ uint32_t s_dc[12], s_ac[256], s_w[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    s_ac[t] = tab->ac[t];
+    if (t < 12) s_dc[t] = tab->dc[t];
+    __syncthreads();
+    const size_t seg = (size_t)blockIdx.y * g.nseg + blockIdx.x;
+    const int16_t* lv = levels + seg * g.bps * 64;
+    uint32_t* bo = boff + seg * g.bps;
+    const int zrl = (int)(s_ac[0xF0] >> 16);
+    for (int j = wave; j < g.bps; j += 4) {
+        const int v = lv[(size_t)j * 64 + lane];
+        const int pred = lane == 0 ? dc_pred(lv, j, g.gray) : 0;
+        const LaneCode c = lane_code(v, lane, pred, s_dc, s_ac);
+        const uint32_t inc = wave_incl_scan((uint32_t)(c.nzrl * zrl + c.n), lane);
+        if (lane == 63) bo[j] = inc;
+    }
+    __syncthreads();
+    uint32_t carry = 0;
+    for (int c0 = 0; c0 < g.bps; c0 += 256) {
+        const int j = c0 + t;
+        const uint32_t v = j < g.bps ? bo[j] : 0u;
+        uint32_t tot;
+        const uint32_t ex = block_excl_scan(v, s_w, &tot);
+        if (j < g.bps) bo[j] = carry + ex;
+        carry += tot;
+    }
+    if (t == 0) segbits[seg] = carry;
+}
+
+// ---- k_jpeg_pack ------------------------------------------------------------------
+constexpr int kPackDwords = (kJpegChunk * kJpegMaxBlockBits + 8 + 31) / 32 + 2;
+
+// OR the low n (<= 32) bits of v into the MSB-first bit buffer at bit `pos`.
+__device__ __forceinline__ void put_bits(uint32_t* buf, uint32_t pos, uint32_t v, int n)
+{
+    if (n <= 0) return;
+    const uint32_t w = pos >> 5;
+    if (w + 1 >= (uint32_t)kPackDwords) return;   // (cannot happen: the buffer holds a chunk's worst case)
+    const unsigned long long x = ((unsigned long long)v << (64 - n)) >> (pos & 31);
+    const uint32_t hi = (uint32_t)(x >> 32), lo = (uint32_t)x;
+    if (hi) atomicOr(&buf[w], hi);
+    if (lo) atomicOr(&buf[w + 1], lo);
+}
+
+// One workgroup per (segment, frame). Chunks of kJpegChunk blocks: the codes are
+// OR-ed into LDS at their bit offsets (neighbouring lanes share dwords: LDS
+// atomics), then the chunk's whole bytes are written out with every 0xFF
+// followed by 0x00; the partial last byte is carried into the next chunk, and
+// the segment's last byte is padded with 1-bits.
+__global__ __launch_bounds__(256) void k_jpeg_pack(JpegGeom g, const JpegTables* __restrict__ tab,
+                                                   const int16_t* __restrict__ levels,
+                                                   const uint32_t* __restrict__ boff,
+                                                   const uint32_t* __restrict__ segbits, uint8_t* __restrict__ scratch,
+                                                   uint32_t* __restrict__ seglen)
+{
+    __shared__ uint32_t s_dc[12], s_ac[256], s_w[4];
+    __shared__ uint32_t s_buf[kPackDwords];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    s_ac[t] = tab->ac[t];
+    if (t < 12) s_dc[t] = tab->dc[t];
+    const size_t seg = (size_t)blockIdx.y * g.nseg + blockIdx.x;
+    const int16_t* lv = levels + seg * g.bps * 64;
+    const uint32_t* bo = boff + seg * g.bps;
+    uint8_t* dst = scratch + seg * g.segcap;
+    const uint32_t total = segbits[seg];
+    __syncthreads();
+    const uint32_t zrl_code = s_ac[0xF0] & 0xffffu;
+    const int zrl = (int)(s_ac[0xF0] >> 16);
+    uint32_t carry = 0, outpos = 0;
+    for (int c0 = 0; c0 < g.bps; c0 += kJpegChunk) {
+        const int cnt = min(kJpegChunk, g.bps - c0);
+        const bool last = c0 + cnt == g.bps;
+        const uint32_t bit0 = bo[c0] & ~7u, bit1 = last ? total : bo[c0 + cnt];
+        const uint32_t span = bit1 - bit0;
+        const int nd = (int)min((uint32_t)kPackDwords, (span + 31) / 32 + 2);
+        for (int i = t; i < nd; i += 256) s_buf[i] = i == 0 ? carry << 24 : 0u;
+        __syncthreads();
+        for (int j = wave; j < cnt; j += 4) {
+            const int v = lv[(size_t)(c0 + j) * 64 + lane];
+            const int pred = lane == 0 ? dc_pred(lv, c0 + j, g.gray) : 0;
+            const LaneCode c = lane_code(v, lane, pred, s_dc, s_ac);
+            const uint32_t mine = (uint32_t)(c.nzrl * zrl + c.n);
+            uint32_t pos = bo[c0 + j] - bit0 + wave_incl_scan(mine, lane) - mine;
+            for (int z = 0; z < c.nzrl; ++z, pos += zrl) put_bits(s_buf, pos, zrl_code, zrl);
+            put_bits(s_buf, pos, c.code, c.n);
+        }
+        if (last && t == 0) {
+            const int npad = (int)((0u - span) & 7u);
+            put_bits(s_buf, span, (1u << npad) - 1u, npad);
+        }
+        __syncthreads();
+        const uint32_t nbytes = last ? (span + 7) >> 3 : span >> 3;
+        carry = last ? 0u : (s_buf[nbytes >> 2] >> (24 - 8 * (nbytes & 3))) & 0xffu;
+        for (uint32_t base = 0; base < nbytes; base += 1024) {
+            const uint32_t idx = (base >> 2) + t;
+            const int nv = idx * 4 < nbytes ? (int)min(4u, nbytes - idx * 4) : 0;
+            const uint32_t v = nv ? s_buf[idx] : 0u;
+            uint32_t cntb = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < nv) cntb += 1 + (((v >> (24 - 8 * i)) & 0xffu) == 0xffu);
+            uint32_t tot;
+            uint32_t p = outpos + block_excl_scan(cntb, s_w, &tot);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < nv) {
+                    const uint32_t b = (v >> (24 - 8 * i)) & 0xffu;
+                    if (p < g.segcap) dst[p] = (uint8_t)b;
+                    ++p;
+                    if (b == 0xffu) {
+                        if (p < g.segcap) dst[p] = 0;
+                        ++p;
+                    }
+                }
+            outpos += tot;
+        }
+        __syncthreads();   // s_buf is zeroed next
+    }
+    if (t == 0) seglen[seg] = outpos;
+}
+
+// ---- k_jpeg_gather ----------------------------------------------------------------
+// One workgroup per (segment, frame): the segment's place is the sum of the
+// lengths before it plus their 2-byte RST markers; the last segment is followed
+// by EOI. A frame that does not fit its slot is not written at all.
+__global__ __launch_bounds__(256) void k_jpeg_gather(JpegGeom g, const uint8_t* __restrict__ scratch,
+                                                     const uint32_t* __restrict__ seglen, uint8_t* __restrict__ out,
+                                                     size_t out_stride, uint32_t* __restrict__ sizes,
+                                                     uint32_t* __restrict__ overflow)
+{
+    __shared__ uint32_t s_w[4];
+    const int t = threadIdx.x, s = blockIdx.x;
+    const uint32_t* sl = seglen + (size_t)blockIdx.y * g.nseg;
+    uint32_t before = 0, all = 0;
+    for (int i = t; i < g.nseg; i += 256) {
+        const uint32_t n = sl[i] + 2u;   // its RST marker, or EOI after the last
+        all += n;
+        if (i < s) before += n;
+    }
+    uint32_t need, pre;
+    (void)block_excl_scan(all, s_w, &need);
+    (void)block_excl_scan(before, s_w, &pre);
+    const bool fits = (size_t)need <= out_stride;
+    if (s == 0 && t == 0) {
+        sizes[blockIdx.y] = need;
+        if (!fits) *overflow = 1u;
+    }
+    if (!fits) return;
+    const uint32_t len = sl[s];
+    const uint8_t* src = scratch + ((size_t)blockIdx.y * g.nseg + s) * g.segcap;
+    uint8_t* dst = out + (size_t)blockIdx.y * out_stride + pre;
+    for (uint32_t i = t; i < len; i += 256) dst[i] = src[i];
+    if (t == 0) {
+        dst[len] = 0xff;
+        dst[len + 1] = s == g.nseg - 1 ? (uint8_t)0xd9 : (uint8_t)(0xd0 + (s & 7));
+    }
+}
+
+}  // namespace
+
+hipError_t jpeg_launch_dct(const uint8_t* frames, size_t pitch, size_t fstride, int n, const JpegGeom& g,
+                           const JpegTables* tab, const JpegBufs& b, hipStream_t st)
+{
+    const int aligned = pitch % 4 == 0 && ((uintptr_t)frames & 3) == 0 && (n <= 1 || fstride % 4 == 0);
+    const dim3 grid((unsigned)((g.units_x * g.nseg + 3) / 4), (unsigned)n);
+    if (g.gray)
+        hipLaunchKernelGGL(k_jpeg_dct<true>, grid, dim3(256), 0, st, frames, pitch, fstride, g, tab, b.levels, aligned);
+    else
+        hipLaunchKernelGGL(k_jpeg_dct<false>, grid, dim3(256), 0, st, frames, pitch, fstride, g, tab, b.levels, aligned);
+    return hipGetLastError();
+}
+
+hipError_t jpeg_launch_bits(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_jpeg_bits, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, tab, b.levels, b.boff,
+                       b.segbits);
+    return hipGetLastError();
+}
+
+hipError_t jpeg_launch_pack(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_jpeg_pack, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, tab, b.levels, b.boff,
+                       b.segbits, b.scratch, b.seglen);
+    return hipGetLastError();
+}
+
+hipError_t jpeg_launch_gather(int n, const JpegGeom& g, const JpegBufs& b, uint8_t* out, size_t out_stride,
+                              uint32_t* sizes, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_jpeg_gather, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, b.scratch, b.seglen,
+                       out, out_stride, sizes, b.overflow);
+    return hipGetLastError();
+}
+
+}  // namespace dvc

@@ -18,7 +18,17 @@ the accelerated path. Here:
   (same basename) so every output frame is still inspectable, or — with
   ``DVC_VIDEO_SINK=y4m`` or a ``.y4m`` name — as a YUV4MPEG2 video (colour
   frames 4:2:0 via ``dvc_bgr_to_i420`` on the GPU = cvtColor BGR2YUV_I420;
-  single-channel frames as ``Cmono``) that any player or encoder reads.
+  single-channel frames as ``Cmono``) that any player or encoder reads, or —
+  with ``DVC_VIDEO_SINK=mjpeg`` — as a real ``.mp4``: Motion-JPEG in ISO BMFF
+  (an ``mp4v`` sample entry whose ``esds`` says objectTypeIndication 0x6C,
+  ISO/IEC 10918-1), every frame a baseline JPEG encoded on the GPU by
+  ``dvc_jpeg_encode`` at ``DVC_VIDEO_QUALITY`` (default 75). These are not the
+  reference's MPEG-4 Part 2 files (intra-only, another codec: sizes are not
+  comparable with its), but they are compressed, so the size reduction
+  ``performance_analysis`` reports means something;
+* such an ``.mp4`` is readable again (``Mp4MjpegReader``: the samples demuxed
+  here, decoded by Pillow when it is importable) — the OF driver's second pass
+  and ``performance_analysis`` read the files the first pass wrote.
 """
 from __future__ import annotations
 
@@ -211,6 +221,244 @@ class Y4mWriter:
             self._fp = None
 
 
+def _box(kind: bytes, *payload: bytes) -> bytes:
+    body = b"".join(payload)
+    return struct.pack(">I4s", 8 + len(body), kind) + body
+
+
+def _full(kind: bytes, version_flags: int, *payload: bytes) -> bytes:
+    return _box(kind, struct.pack(">I", version_flags), *payload)
+
+
+_MATRIX = struct.pack(">9I", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000)
+_FTYP = _box(b"ftyp", b"isom", struct.pack(">I", 0x200), b"isom", b"iso2", b"mp41")
+
+
+def fps_ratio(fps: float):
+    """(timescale, ticks per frame) — the ratio Y4mWriter writes as F<num>:<den>."""
+    num, den = (int(round(float(fps) * 1000)), 1000) if float(fps) != int(fps) else (int(fps), 1)
+    return max(num, 1), den
+
+
+class Mp4Muxer:
+    """ISO BMFF writer of one Motion-JPEG video track: ``ftyp``, an ``mdat``
+    streamed to disk (one sample = one chunk per frame; its 64-bit size patched
+    at close), then ``moov`` with the sample tables. ``add_sample`` takes one
+    complete JPEG image."""
+
+    def __init__(self, path: str, fps: float, size):
+        self.path, self.W, self.H = path, int(size[0]), int(size[1])
+        self.timescale, self.delta = fps_ratio(fps)
+        self.sizes, self.offsets = [], []
+        self._fp = open(path, "wb")
+        self._fp.write(_FTYP)
+        self._mdat = self._fp.tell()
+        self._fp.write(struct.pack(">I4sQ", 1, b"mdat", 16))   # largesize form
+
+    def add_sample(self, data: bytes) -> None:
+        self.offsets.append(self._fp.tell())
+        self.sizes.append(len(data))
+        self._fp.write(data)
+
+    def _moov(self) -> bytes:
+        n, dur = len(self.sizes), len(self.sizes) * self.delta
+        # ES_Descriptor { ES_ID 1; DecoderConfigDescriptor { objectTypeIndication 0x6C = Visual
+        # ISO/IEC 10918-1 (JPEG), streamType 4 (visual) }; SLConfigDescriptor { predefined 2 } }
+        dcfg = struct.pack(">BBBB3sII", 0x04, 13, 0x6C, 0x11, b"\0\0\0", 0, 0)
+        esds = _full(b"esds", 0, struct.pack(">BBHB", 0x03, 3 + len(dcfg) + 3, 1, 0), dcfg, b"\x06\x01\x02")
+        mp4v = _box(b"mp4v", b"\0" * 6, struct.pack(">H", 1), b"\0" * 16, struct.pack(">HHIIIH", self.W, self.H,
+                    0x480000, 0x480000, 0, 1), b"\0" * 32, struct.pack(">Hh", 24, -1), esds)
+        stbl = _box(b"stbl",
+                    _full(b"stsd", 0, struct.pack(">I", 1), mp4v),
+                    _full(b"stts", 0, struct.pack(">III", 1, n, self.delta)),
+                    _full(b"stsc", 0, struct.pack(">IIII", 1, 1, 1, 1)),
+                    _full(b"stsz", 0, struct.pack(">II", 0, n), struct.pack(">%dI" % n, *self.sizes)),
+                    _full(b"co64", 0, struct.pack(">I", n), struct.pack(">%dQ" % n, *self.offsets)))
+        minf = _box(b"minf", _full(b"vmhd", 1, b"\0" * 8),
+                    _box(b"dinf", _full(b"dref", 0, struct.pack(">I", 1), _full(b"url ", 1))), stbl)
+        mdia = _box(b"mdia", _full(b"mdhd", 0, struct.pack(">IIIIHH", 0, 0, self.timescale, dur, 0x55C4, 0)),
+                    _full(b"hdlr", 0, struct.pack(">I4s12s", 0, b"vide", b""), b"VideoHandler\0"), minf)
+        tkhd = _full(b"tkhd", 3, struct.pack(">IIIII8sHHHH", 0, 0, 1, 0, dur, b"", 0, 0, 0, 0), _MATRIX,
+                     struct.pack(">II", self.W << 16, self.H << 16))
+        mvhd = _full(b"mvhd", 0, struct.pack(">IIIIIH10s", 0, 0, self.timescale, dur, 0x10000, 0x100, b""), _MATRIX,
+                     b"\0" * 24, struct.pack(">I", 2))
+        return _box(b"moov", mvhd, _box(b"trak", tkhd, mdia))
+
+    def close(self) -> None:
+        if self._fp is None:
+            return
+        end = self._fp.tell()
+        self._fp.write(self._moov())
+        self._fp.seek(self._mdat + 8)
+        self._fp.write(struct.pack(">Q", end - self._mdat))
+        self._fp.close()
+        self._fp = None
+
+
+class Mp4MjpegWriter:
+    """cv2.VideoWriter-like writer of a Motion-JPEG ``.mp4``: frames (BGR, or
+    single-channel when ``is_color`` is false) are JPEG-encoded on the GPU in
+    batches of ``batch`` (the rest at release) and muxed by :class:`Mp4Muxer`.
+    ``encoder``: anything with ``header`` and ``encode(frames) -> [bytes]``
+    (default: :class:`_native.JpegEncoder` on ``device``)."""
+
+    def __init__(self, path: str, fps: float, size, is_color: bool = True, device: int = 0, quality: int = 75,
+                 batch: int = 8, encoder=None):
+        self.path, self.W, self.H, self.is_color = path, int(size[0]), int(size[1]), bool(is_color)
+        self.n, self._batch, self._fill = 0, max(1, int(batch)), 0
+        if encoder is None:
+            from ._native import JpegEncoder
+            encoder = JpegEncoder(self.W, self.H, self.is_color, quality, self._batch, device)
+        self._enc = encoder
+        self._shape = (self.H, self.W, 3) if self.is_color else (self.H, self.W)
+        # the pending batch; the GPU encoder hands out page-locked memory for it
+        self._buf = getattr(encoder, "alloc", lambda s: np.empty(s, np.uint8))((self._batch,) + self._shape)
+        self._mux = Mp4Muxer(path, fps, size)
+
+    def isOpened(self) -> bool:
+        return self._mux is not None
+
+    def _flush(self) -> None:
+        if self._fill:
+            n, self._fill = self._fill, 0
+            for payload in self._enc.encode(self._buf[:n]):
+                self._mux.add_sample(self._enc.header + payload)
+
+    def write(self, frame: np.ndarray) -> None:
+        if self._mux is None:
+            return
+        if frame.shape != self._shape:   # cv2.VideoWriter silently drops mismatched frames
+            return
+        self._buf[self._fill] = frame
+        self._fill += 1
+        self.n += 1
+        if self._fill >= self._batch:
+            self._flush()
+
+    def release(self) -> None:
+        if self._mux is None:
+            return
+        try:
+            self._flush()
+        finally:
+            self._mux.close()
+            self._mux = None
+            if hasattr(self._enc, "close"):
+                self._enc.close()
+
+
+def _child_boxes(buf, start, end):
+    """(kind, payload start, box end) of the boxes in buf[start:end]."""
+    p = start
+    while p + 8 <= end:
+        size, kind = struct.unpack_from(">I4s", buf, p)
+        head = 8
+        if size == 1:
+            size, head = struct.unpack_from(">Q", buf, p + 8)[0], 16
+        elif size == 0:
+            size = end - p
+        if size < head or p + size > end:
+            return
+        yield kind, p + head, p + size
+        p += size
+
+
+def _find(buf, start, end, *kinds):
+    for k in kinds:
+        hit = next(((a, b) for kind, a, b in _child_boxes(buf, start, end) if kind == k), None)
+        if hit is None:
+            return None
+        start, end = hit
+    return start, end
+
+
+class Mp4MjpegReader:
+    """cv2.VideoCapture-like reader of the files :class:`Mp4MjpegWriter` writes
+    (``ftyp``, one video track, an ``mp4v`` entry whose ``esds`` says 0x6C, one
+    sample per chunk). Samples are demuxed here and decoded by Pillow: colour
+    to BGR, a single-component stream to a 2-D array. Without Pillow, or on any
+    other file, the reader does not open."""
+
+    def __init__(self, path: str):
+        self._fp, self._i, self.samples = None, 0, []
+        try:
+            from PIL import Image
+            self._Image = Image
+            self._parse(path)
+        except Exception:
+            if self._fp is not None:
+                self._fp.close()
+            self._fp = None
+
+    def _parse(self, path):
+        fp = open(path, "rb")
+        self._fp = fp
+        head = fp.read(len(_FTYP) + 16)
+        if head[:len(_FTYP)] != _FTYP or head[len(_FTYP) + 4:len(_FTYP) + 8] != b"mdat":
+            raise ValueError("not a file of Mp4MjpegWriter")
+        size = struct.unpack_from(">I", head, len(_FTYP))[0]
+        if size == 1:
+            size = struct.unpack_from(">Q", head, len(_FTYP) + 8)[0]
+        fp.seek(len(_FTYP) + size)
+        moov = fp.read()
+        top = _find(moov, 0, len(moov), b"moov", b"trak", b"mdia")
+        mdhd = _find(moov, *top, b"mdhd")
+        stbl = _find(moov, *top, b"minf", b"stbl")
+        timescale = struct.unpack_from(">I", moov, mdhd[0] + 12)[0]
+        box = {k: _find(moov, *stbl, k) for k in (b"stsd", b"stts", b"stsc", b"stsz", b"co64")}
+        entry = next(_child_boxes(moov, box[b"stsd"][0] + 8, box[b"stsd"][1]))
+        if entry[0] != b"mp4v":
+            raise ValueError("not an mp4v track")
+        self.W, self.H = struct.unpack_from(">HH", moov, entry[1] + 24)
+        esds = _find(moov, entry[1] + 78, entry[2], b"esds")
+        e = moov[esds[0] + 4:esds[1]]
+        if not (e[0] == 0x03 and e[5] == 0x04 and e[7] == 0x6C):
+            raise ValueError("not objectTypeIndication 0x6C")
+        count, nsamp, delta = struct.unpack_from(">III", moov, box[b"stts"][0] + 4)
+        if struct.unpack_from(">IIII", moov, box[b"stsc"][0] + 4) != (1, 1, 1, 1) or count != 1:
+            raise ValueError("unexpected sample tables")
+        fixed, n = struct.unpack_from(">II", moov, box[b"stsz"][0] + 4)
+        sizes = [fixed] * n if fixed else list(struct.unpack_from(">%dI" % n, moov, box[b"stsz"][0] + 12))
+        offs = list(struct.unpack_from(">%dQ" % n, moov, box[b"co64"][0] + 8))
+        if n != nsamp or len(offs) != n:
+            raise ValueError("inconsistent sample tables")
+        self.fps = timescale / delta if delta else 0.0
+        self.samples = list(zip(offs, sizes))
+
+    def isOpened(self) -> bool:
+        return self._fp is not None
+
+    def get(self, prop: int) -> float:
+        if self._fp is None:
+            return 0.0
+        return {CAP_PROP_FPS: self.fps, CAP_PROP_FRAME_WIDTH: float(self.W), CAP_PROP_FRAME_HEIGHT: float(self.H),
+                CAP_PROP_FRAME_COUNT: float(len(self.samples))}.get(prop, 0.0)
+
+    def read_sample(self):
+        """(ok, the next sample's bytes: one JPEG image)."""
+        if self._fp is None or self._i >= len(self.samples):
+            return False, None
+        off, size = self.samples[self._i]
+        self._i += 1
+        self._fp.seek(off)
+        return True, self._fp.read(size)
+
+    def read(self):
+        import io
+        ok, data = self.read_sample()
+        if not ok:
+            return False, None
+        im = self._Image.open(io.BytesIO(data))
+        if im.mode == "L":
+            return True, np.asarray(im)
+        return True, np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
+
+    def release(self) -> None:
+        if self._fp is not None:
+            self._fp.close()
+            self._fp = None
+
+
 def video_name(path: str) -> str:
     """<basename without extension> (fd:45, fd:177); a synthetic URI is named WxH."""
     if path.startswith("synthetic://"):
@@ -229,6 +477,10 @@ def open_source(path: str):
         q = {k: v[0] for k, v in parse_qs(u.query).items()}
         clip = SyntheticClip(w, h, seed=int(q.get("seed", 0)), noisy=q.get("noisy", "0") in ("1", "true"))
         return _ArraySource(_SyntheticFrames(clip, int(q.get("frames", 100))), float(q.get("fps", 30)))
+    if not path.endswith(".npy") and cv2 is None and os.path.isfile(path):
+        r = Mp4MjpegReader(path)   # a Motion-JPEG .mp4 of this package (DVC_VIDEO_SINK=mjpeg)
+        if r.isOpened():
+            return r
     if not path.endswith(".npy") and cv2 is None:
         # an .mp4 this package wrote without OpenCV is the .npy / .y4m stream next to it
         for ext in (".npy", ".y4m"):
@@ -301,6 +553,9 @@ def open_sink(path: str, fps: float, size, is_color: bool = True):
     if ext == ".y4m" or (ext != ".npy" and cv2 is None and os.environ.get("DVC_VIDEO_SINK", "npy") == "y4m"):
         dev = int(os.environ.get("DVC_DEVICE", os.environ.get("LOCAL_RANK", 0)))
         return Y4mWriter(root + ".y4m", fps, size, is_color, dev)
+    if ext != ".npy" and cv2 is None and os.environ.get("DVC_VIDEO_SINK", "npy") == "mjpeg":
+        dev = int(os.environ.get("DVC_DEVICE", os.environ.get("LOCAL_RANK", 0)))
+        return Mp4MjpegWriter(path, fps, size, is_color, dev, int(os.environ.get("DVC_VIDEO_QUALITY", 75)))
     if cv2 is not None and ext != ".npy":
         fourcc = cv2.VideoWriter_fourcc(*"mp4v")
         return cv2.VideoWriter(path, fourcc, fps, tuple(size), isColor=is_color)

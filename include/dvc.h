@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define DVC_ABI_VERSION 7
+#define DVC_ABI_VERSION 8
 #define DVC_MAX_BATCH 512
 
 /* ---- status codes ---------------------------------------------------------- */
@@ -104,6 +104,8 @@ extern "C" {
 #define DVC_FMT_BGR  0
 #define DVC_FMT_I420 1
 #define DVC_FMT_NV12 2
+#define DVC_FMT_GRAY 3 /* one 8-bit channel, rows of `pitch` >= W bytes: the mask videos
+                          (of:99-100); an input format of the JPEG encoder only */
 
 /* Standalone conversions (the decode / encode ends of the video I/O), n frames
  * frame_stride (YUV) / bgr_stride (BGR) bytes apart, on `device`:
@@ -463,6 +465,49 @@ int dvc_ofc_run(dvc_ofc* h, const uint8_t* bgr, size_t pitch, size_t frame_strid
                 size_t mask_pitch, size_t mask_stride, int mask_channels, int n, uint8_t* out, size_t out_stride);
 int dvc_ofc_sync(dvc_ofc* h);
 void dvc_ofc_destroy(dvc_ofc* h);
+
+/* ---- Motion-JPEG encoder (the codec end of the video I/O) ---------------------- */
+/* What cv2.VideoWriter(mp4v) does with every frame the reference writes
+ * (frame_differencing.py:63-65,112,131; motion_compression_opt.py:50-52,99-100,
+ * 135-136,185), as baseline JPEG (ISO/IEC 10918-1) on the GPU: one JFIF image per
+ * frame = the handle's constant header (dvc_jpeg_header) + the frame's entropy
+ * data and EOI (dvc_jpeg_encode). The files are Motion-JPEG, not MPEG-4 Part 2.
+ * The arithmetic is integer throughout and specified in DESIGN.md "Motion-JPEG
+ * stream": JFIF full-range YCbCr, 4:2:0 (DVC_FMT_BGR) or one component
+ * (DVC_FMT_GRAY), an exact integer DCT, IJG quality scaling, the project's fixed
+ * Huffman tables (csrc/jpeg_tables.h), one restart interval per MCU row. */
+typedef struct dvc_jpeg dvc_jpeg;
+
+/* An encoder for width x height frames (1..65520) of DVC_FMT_BGR or DVC_FMT_GRAY,
+ * quality 1..100, max_batch (0/1..DVC_MAX_BATCH) frames per device launch.
+ * hip_stream / flags as dvc_ofc_create (DVC_FLAG_DEVICE_PTRS, DVC_FLAG_JOIN_STREAM).
+ * device < 0: a host-only handle that touches no GPU; only dvc_jpeg_header works
+ * on it. Replaces the VideoWriter constructions at fd:63-65 and of:50-52,135-136. */
+int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, int device, void* hip_stream,
+                    uint32_t flags, dvc_jpeg** out);
+void dvc_jpeg_destroy(dvc_jpeg* h);
+
+/* SOI, APP0 (JFIF), two DQT, SOF0, two DHT, DRI and the SOS header: the bytes in
+ * front of every frame's entropy data, constant per handle. Host only. *n
+ * receives the length; dst may be NULL to query it. */
+int dvc_jpeg_header(const dvc_jpeg* h, uint8_t* dst, size_t cap, size_t* n);
+
+/* The worst-case bytes dvc_jpeg_encode writes for one frame (entropy data with
+ * every byte stuffed, RST markers, EOI): an out_stride that always fits. Host only. */
+int dvc_jpeg_bound(int width, int height, int fmt, size_t* bytes);
+
+/* Encode n frames (frame t at frames + t*frame_stride, rows of `pitch` >= 3*W or
+ * W bytes; any pitch and alignment): frame t's entropy data followed by EOI at
+ * out + t*out_stride, its length in sizes[t] (replaces VideoWriter.write at
+ * fd:112,131 and of:99-100,185). Host pointers: returns after the outputs have
+ * landed. DVC_FLAG_DEVICE_PTRS: frames, out and sizes are device pointers and the
+ * call is asynchronous on the handle's stream (the caller's when one was joined).
+ * A frame that needs more than out_stride bytes is not written (nothing is
+ * written past a slot), sizes[t] still holds the needed length, and the call
+ * returns DVC_E_NOMEM — with device pointers the next dvc_jpeg_sync does. */
+int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t frame_stride, int n, uint8_t* out,
+                    size_t out_stride, uint32_t* sizes);
+int dvc_jpeg_sync(dvc_jpeg* h);
 
 /* The Q8 fixed-point Gaussian taps OpenCV's bit-exact 8U GaussianBlur uses
  * (getGaussianKernelBitExact + error-diffusion rounding to 8 fraction bits).

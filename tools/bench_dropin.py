@@ -1,8 +1,8 @@
 """Drop-in driver throughput (GPU box): process_single_video_fd (or _of) end to
 end as a user calls it — a 1080p Y4M (4:2:0) camera file in, the two output videos out
-(.npy streams of BGR frames, or Y4M with DVC_VIDEO_SINK=y4m), file I/O and host
-copies included. Prints one JSON line per run.
-  python tools/bench_dropin.py [--frames N] [--sink npy|y4m] [--module NAME] [--dir /tmp/x]
+(.npy streams of BGR frames, Y4M with DVC_VIDEO_SINK=y4m, or Motion-JPEG .mp4 with
+DVC_VIDEO_SINK=mjpeg), file I/O and host copies included. Prints one JSON line per run.
+  python tools/bench_dropin.py [--frames N] [--sink npy|y4m|mjpeg] [--module NAME] [--dir /tmp/x]
 """
 import argparse
 import importlib
@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--frames", type=int, default=150)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--sink", choices=("npy", "y4m"), default="npy")
+    ap.add_argument("--sink", choices=("npy", "y4m", "mjpeg"), default="npy")
     ap.add_argument("--path", choices=("fd", "of"), default="fd")
     ap.add_argument("--module", default="")
     ap.add_argument("--dir", default="/tmp/dvc_dropin")

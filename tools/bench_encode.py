@@ -1,0 +1,126 @@
+"""Motion-JPEG encoder throughput (GPU box): dvc_jpeg_encode on device-resident
+1080p BGR frames of the synthetic clip, batches of 32, device pointers on a
+joined stream, timed with device events around `steps` calls (5 runs after a
+warm-up). Prints one JSON line: encode Mpx/s and frames/s, the bytes moved per
+second against dvc_copy_rate on the same box, and — with --kernels, from a
+second run of this script under rocprofv3 --kernel-trace --stats — the time of
+each kernel per batch.
+  python tools/bench_encode.py [--kernels] [--out FILE] [--width W --height H --batch B --quality Q]
+"""
+import argparse
+import csv
+import ctypes
+import glob
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+
+
+def kernel_times(a):
+    """{kernel: microseconds per launch} from a profiled child run (3 steps)."""
+    d = tempfile.mkdtemp(prefix="dvc_jpeg_prof_")
+    try:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "t", "--output-format", "csv", "--",
+               sys.executable, os.path.abspath(__file__), "--steps", "3", "--runs", "1", "--no-copy-rate",
+               "--width", str(a.width), "--height", str(a.height), "--batch", str(a.batch), "--quality", str(a.quality)]
+        subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, timeout=300)
+        out = {}
+        for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+            for row in csv.DictReader(open(path)):
+                if "k_jpeg_" in row["Name"]:
+                    name = "k_jpeg_" + row["Name"].split("k_jpeg_")[1].split("(")[0].split("<")[0]
+                    out[name] = {"us_per_launch": round(float(row["AverageNs"]) / 1e3, 1), "launches": int(row["Calls"])}
+        return out
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--quality", type=int, default=75)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--no-copy-rate", action="store_true")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from dvc_amd import _native as N
+    from dvc_amd.synthetic import SyntheticClip
+
+    W, H, B = a.width, a.height, a.batch
+    L = N.lib()
+    clip = SyntheticClip(W, H, seed=0)
+    frames = torch.from_numpy(np.stack([clip.frame(t) for t in range(B)])).cuda()
+    bound = ctypes.c_size_t()
+    N.check(L.dvc_jpeg_bound(W, H, N.FMT_BGR, ctypes.byref(bound)))
+    stride = (bound.value + 255) & ~255
+    out = torch.empty((B, stride), dtype=torch.uint8, device="cuda")
+    sizes = torch.zeros(B, dtype=torch.int32, device="cuda")
+    s = torch.cuda.Stream()
+    h = ctypes.c_void_p()
+    N.check(L.dvc_jpeg_create(W, H, N.FMT_BGR, a.quality, B, 0, ctypes.c_void_p(s.cuda_stream), N.DVC_FLAG_DEVICE_PTRS,
+                              ctypes.byref(h)))
+
+    def call():
+        N.check(L.dvc_jpeg_encode(h, frames.data_ptr(), 3 * W, 3 * W * H, B, out.data_ptr(), stride, sizes.data_ptr()))
+
+    with torch.cuda.stream(s):
+        for _ in range(a.warmup):
+            call()
+        s.synchronize()
+        ms = []
+        for _ in range(a.runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            for _ in range(a.steps):
+                call()
+            e1.record(s)
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1) / a.steps)
+    N.check(L.dvc_jpeg_sync(h))
+    L.dvc_jpeg_destroy(h)
+    out_bytes = int(sizes.cpu().numpy().astype(np.int64).sum())
+    best = float(np.median(ms))
+    px = B * W * H
+    # bytes the four kernels move per batch: BGR in; levels (int16, 1.5 samples per pixel) written once and
+    # read twice; block offsets written twice, read twice; the stream written to scratch, read, written out
+    nblk = px * 1.5 / 64
+    pipeline = 3 * px + 3 * 3 * px + 4 * 4 * nblk + 3 * out_bytes
+    res = {
+        "metric": "Motion-JPEG encode, device-resident BGR -> entropy data (dvc_jpeg_encode)",
+        "value": round(px / best / 1e3, 1), "unit": "Mpixels/s",
+        "frames_per_s": round(B / best * 1e3, 1), "ms_per_batch": round(best, 4),
+        "timing": {"ms_per_batch_per_run": [round(m, 4) for m in ms], "steps": a.steps, "warmup": a.warmup,
+                   "value_per_run": [round(px / m / 1e3, 1) for m in ms], "timed_with": "device events, joined stream"},
+        "config": {"width": W, "height": H, "batch": B, "quality": a.quality, "data": "synthetic clip seed 0",
+                   "io": "device"},
+        "compressed_bytes_per_frame": round(out_bytes / B), "bits_per_pixel": round(8 * out_bytes / px, 3),
+        "algorithmic_GBps": round((3 * px + out_bytes) / best / 1e6, 1),
+        "pipeline_GBps": round(pipeline / best / 1e6, 1),
+    }
+    if not a.no_copy_rate:
+        res["copy_rate_GBps"] = round(N.copy_rate(0), 1)
+        res["pipeline_frac_of_copy_rate"] = round(res["pipeline_GBps"] / res["copy_rate_GBps"], 4)
+    if a.kernels:
+        res["kernels"] = kernel_times(a)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
