@@ -17,9 +17,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdvc_hip.so")
 SOURCES = ["fd_kernels.hip", "fd_api.hip", "of_kernels.hip", "of_api.hip", "yuv_kernels.hip", "diag.hip",
-           "jpeg_kernels.hip", "jpeg_api.hip"]
+           "jpeg_kernels.hip", "jpeg_api.hip", "jpegd_kernels.hip", "jpegd_api.hip"]
 HEADERS = ["fd_kernels.h", "dvc_device.h", "of_kernels.h", "host_common.h", "yuv_kernels.h", "yuv_px.h",
-           "jpeg_kernels.h", "jpeg_tables.h"]
+           "jpeg_kernels.h", "jpeg_tables.h", "jpegd_kernels.h", "jpegd_core.h", "jpegd_header.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 DVC_OK = 0
@@ -52,9 +52,10 @@ EXPORTS = [
     "dvc_copy_rate", "dvc_ofc_create", "dvc_ofc_run", "dvc_ofc_sync", "dvc_ofc_destroy",
     "dvc_fd_set_state", "dvc_of_set_state", "dvc_fd_ktime_kernel", "dvc_of_ktime_kernel",
     "dvc_fd_graph_stats", "dvc_jpeg_create", "dvc_jpeg_destroy", "dvc_jpeg_header", "dvc_jpeg_bound",
-    "dvc_jpeg_encode", "dvc_jpeg_sync",
+    "dvc_jpeg_encode", "dvc_jpeg_sync", "dvc_jpegd_create", "dvc_jpegd_destroy", "dvc_jpegd_set_header",
+    "dvc_jpegd_decode", "dvc_jpegd_sync",
 ]
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_BATCH = 512
 
 
@@ -245,6 +246,17 @@ def lib() -> ctypes.CDLL:
     L.dvc_jpeg_encode.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t, vp]
     L.dvc_jpeg_sync.argtypes = [vp]
     for name in ("dvc_jpeg_create", "dvc_jpeg_header", "dvc_jpeg_bound", "dvc_jpeg_encode", "dvc_jpeg_sync"):
+        getattr(L, name).restype = ctypes.c_int
+    L.dvc_jpegd_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint32,
+                                   ctypes.POINTER(vp)]
+    L.dvc_jpegd_destroy.argtypes = [vp]
+    L.dvc_jpegd_destroy.restype = None
+    L.dvc_jpegd_set_header.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                       ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_int)]
+    L.dvc_jpegd_decode.argtypes = [vp, u8p, ctypes.c_size_t, vp, ctypes.c_int, u8p, ctypes.c_size_t, ctypes.c_size_t, vp]
+    L.dvc_jpegd_sync.argtypes = [vp]
+    for name in ("dvc_jpegd_create", "dvc_jpegd_set_header", "dvc_jpegd_decode", "dvc_jpegd_sync"):
         getattr(L, name).restype = ctypes.c_int
     L.dvc_bgr_to_i420.restype = ctypes.c_int
     for name in ("dvc_of_create", "dvc_of_prime", "dvc_of_step", "dvc_of_step_batch", "dvc_of_sync",
@@ -455,6 +467,89 @@ class JpegEncoder:
     def close(self):
         if getattr(self, "_h", None):
             lib().dvc_jpeg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class JpegDecoder:
+    """cv2.VideoCapture's codec end on the GPU (dvc_jpegd): whole JPEG samples
+    (``bytes``, as Mp4MjpegReader.read_sample returns them) -> numpy frames,
+    (H, W, 3) BGR or (H, W) for a single-component stream, the bytes Pillow
+    gives. The header (SOI..SOS) is parsed on the host, again only when a
+    sample's header bytes differ from the last one's; a stream outside the
+    decoder's set raises DvcError with code DVC_E_UNSUPPORTED."""
+
+    def __init__(self, max_width: int, max_height: int, max_batch: int = 8, device: int = 0):
+        self.max_batch = max(1, int(max_batch))
+        self._h = self._in = self._out = None
+        self._hdr, self.W, self.H, self.fmt = None, 0, 0, FMT_BGR
+        h = ctypes.c_void_p()
+        check(lib().dvc_jpegd_create(int(max_width), int(max_height), self.max_batch, int(device), None, 0,
+                                     ctypes.byref(h)))
+        self._h = h
+
+    def set_header(self, sample: bytes) -> int:
+        """Parse ``sample``'s header; returns its length (where the entropy data starts)."""
+        n, w, hh, fmt = ctypes.c_size_t(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        check(lib().dvc_jpegd_set_header(self._h, sample, len(sample), ctypes.byref(n), ctypes.byref(w), ctypes.byref(hh),
+                                         ctypes.byref(fmt)))
+        self._hdr, self.W, self.H, self.fmt = bytes(sample[:n.value]), w.value, hh.value, fmt.value
+        return n.value
+
+    def _run(self, samples):
+        """Samples that share the current header -> frames (None from the first damaged one on)."""
+        import numpy as np
+        hl, n = len(self._hdr), len(samples)
+        stride = (max(len(s) for s in samples) - hl + 3) & ~3
+        if self._in is None or self._in.shape[0] < n or self._in.shape[1] < stride:
+            self._in = pinned((max(n, self.max_batch), max(stride, 4096)))
+        shape = (self.H, self.W, 3) if self.fmt == FMT_BGR else (self.H, self.W)
+        if self._out is None or self._out.shape[0] < n or self._out.shape[1:] != shape:
+            self._out = pinned((max(n, self.max_batch),) + shape)
+        sizes, status = np.zeros(n, np.uint32), np.zeros(n, np.int32)
+        for i, s in enumerate(samples):
+            sizes[i] = len(s) - hl
+            self._in[i, :sizes[i]] = np.frombuffer(s, np.uint8, sizes[i], hl)
+        out = self._out
+        rc = lib().dvc_jpegd_decode(self._h, self._in.ctypes.data, self._in.shape[1], sizes.ctypes.data, n,
+                                    out.ctypes.data, out[0][0].nbytes, out[0].nbytes, status.ctypes.data)
+        if rc != DVC_OK and not status.any():
+            check(rc)
+        return [out[i].copy() if status[i] == 0 else None for i in range(n)]
+
+    def decode(self, samples) -> list:
+        """One frame per sample; ``None`` for a sample whose data is damaged."""
+        frames, run = [], []
+        for s in list(samples) + [None]:
+            same = s is not None and self._hdr is not None and len(s) > len(self._hdr) and \
+                s[:len(self._hdr)] == self._hdr
+            if run and not same:
+                frames += self._run(run)
+                run = []
+            if s is None:
+                break
+            if not same:
+                try:
+                    hl = self.set_header(s)
+                except DvcError as e:
+                    if e.code == DVC_E_UNSUPPORTED:
+                        raise
+                    frames.append(None)      # no header: a damaged sample
+                    continue
+                if len(s) <= hl:
+                    frames.append(None)
+                    continue
+            run.append(s)
+        return frames
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dvc_jpegd_destroy(self._h)
             self._h = None
 
     def __del__(self):

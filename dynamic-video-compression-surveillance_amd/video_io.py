@@ -27,8 +27,9 @@ the accelerated path. Here:
   comparable with its), but they are compressed, so the size reduction
   ``performance_analysis`` reports means something;
 * such an ``.mp4`` is readable again (``Mp4MjpegReader``: the samples demuxed
-  here, decoded by Pillow when it is importable) — the OF driver's second pass
-  and ``performance_analysis`` read the files the first pass wrote.
+  here, decoded in batches on the GPU by ``dvc_jpegd_decode``, or by Pillow —
+  the same bytes; ``DVC_MJPEG_DECODE=auto|gpu|pillow``) — the OF driver's
+  second pass and ``performance_analysis`` read the files the first pass wrote.
 """
 from __future__ import annotations
 
@@ -372,18 +373,50 @@ def _find(buf, start, end, *kinds):
     return start, end
 
 
+_GPU_DECODE = None
+
+
+def _gpu_decode_available() -> bool:
+    """Whether DVC_MJPEG_DECODE=auto decodes on the GPU: the library loads and a device exists."""
+    global _GPU_DECODE
+    if _GPU_DECODE is None:
+        try:
+            import ctypes
+            from . import _native as N
+            n = ctypes.c_int(0)
+            _GPU_DECODE = N.lib().dvc_device_count(ctypes.byref(n)) == 0 and n.value > 0
+        except Exception:
+            _GPU_DECODE = False
+    return _GPU_DECODE
+
+
 class Mp4MjpegReader:
     """cv2.VideoCapture-like reader of the files :class:`Mp4MjpegWriter` writes
     (``ftyp``, one video track, an ``mp4v`` entry whose ``esds`` says 0x6C, one
-    sample per chunk). Samples are demuxed here and decoded by Pillow: colour
-    to BGR, a single-component stream to a 2-D array. Without Pillow, or on any
-    other file, the reader does not open."""
+    sample per chunk). Samples are demuxed here and decoded ``batch`` at a time
+    on the GPU (:class:`_native.JpegDecoder` on ``device``) or one by one by
+    Pillow — the same bytes either way: colour to BGR, a single-component
+    stream to a 2-D array. ``DVC_MJPEG_DECODE`` chooses: ``gpu``, ``pillow``,
+    or ``auto`` (the default): the GPU when the library loads and a device
+    exists, Pillow otherwise and for a file whose JPEG streams the GPU decoder
+    does not take. A sample that does not decode ends the stream. Without a
+    decoder, or on any other file, the reader does not open."""
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, device: int = 0, batch: int = 8):
         self._fp, self._i, self.samples = None, 0, []
+        self._device, self._batch, self._dec, self._ready = int(device), max(1, int(batch)), None, []
         try:
-            from PIL import Image
-            self._Image = Image
+            self._mode = os.environ.get("DVC_MJPEG_DECODE", "auto")
+            if self._mode not in ("auto", "gpu", "pillow"):
+                raise ValueError(f"DVC_MJPEG_DECODE={self._mode}")
+            self._gpu = self._mode == "gpu" or (self._mode == "auto" and _gpu_decode_available())
+            try:
+                from PIL import Image
+                self._Image = Image
+            except ImportError:
+                self._Image = None
+                if not self._gpu:
+                    raise
             self._parse(path)
         except Exception:
             if self._fp is not None:
@@ -435,7 +468,8 @@ class Mp4MjpegReader:
                 CAP_PROP_FRAME_COUNT: float(len(self.samples))}.get(prop, 0.0)
 
     def read_sample(self):
-        """(ok, the next sample's bytes: one JPEG image)."""
+        """(ok, the next sample's bytes: one JPEG image). ``read()`` on the GPU takes
+        its samples from here a batch ahead: use one of the two on a reader."""
         if self._fp is None or self._i >= len(self.samples):
             return False, None
         off, size = self.samples[self._i]
@@ -443,20 +477,55 @@ class Mp4MjpegReader:
         self._fp.seek(off)
         return True, self._fp.read(size)
 
-    def read(self):
+    def _pillow(self, data):
         import io
+        im = self._Image.open(io.BytesIO(data))
+        if im.mode == "L":
+            return np.asarray(im)
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
+
+    def _fill(self) -> None:
+        """Read ahead and decode the next batch on the GPU into self._ready."""
+        from . import _native as N
+        samples = []
+        while len(samples) < self._batch:
+            ok, data = self.read_sample()
+            if not ok:
+                break
+            samples.append(data)
+        if not samples:
+            return
+        if self._dec is None:
+            self._dec = N.JpegDecoder(self.W, self.H, self._batch, self._device)
+        try:
+            self._ready = self._dec.decode(samples)
+        except N.DvcError as e:
+            if e.code != N.DVC_E_UNSUPPORTED or self._mode != "auto" or self._Image is None:
+                raise
+            self._gpu = False                      # a JPEG the GPU decoder does not take: this file goes to Pillow
+            self._i -= len(samples)
+
+    def read(self):
+        if self._gpu:
+            if not self._ready:
+                self._fill()
+            if self._gpu:
+                if not self._ready or self._ready[0] is None:   # the end, or a damaged sample: the stream ends here
+                    self._ready, self._i = [], len(self.samples)
+                    return False, None
+                return True, self._ready.pop(0)
         ok, data = self.read_sample()
         if not ok:
             return False, None
-        im = self._Image.open(io.BytesIO(data))
-        if im.mode == "L":
-            return True, np.asarray(im)
-        return True, np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
+        return True, self._pillow(data)
 
     def release(self) -> None:
         if self._fp is not None:
             self._fp.close()
             self._fp = None
+        if self._dec is not None:
+            self._dec.close()
+            self._dec = None
 
 
 def video_name(path: str) -> str:
@@ -478,7 +547,8 @@ def open_source(path: str):
         clip = SyntheticClip(w, h, seed=int(q.get("seed", 0)), noisy=q.get("noisy", "0") in ("1", "true"))
         return _ArraySource(_SyntheticFrames(clip, int(q.get("frames", 100))), float(q.get("fps", 30)))
     if not path.endswith(".npy") and cv2 is None and os.path.isfile(path):
-        r = Mp4MjpegReader(path)   # a Motion-JPEG .mp4 of this package (DVC_VIDEO_SINK=mjpeg)
+        # a Motion-JPEG .mp4 of this package (DVC_VIDEO_SINK=mjpeg)
+        r = Mp4MjpegReader(path, int(os.environ.get("DVC_DEVICE", os.environ.get("LOCAL_RANK", 0))))
         if r.isOpened():
             return r
     if not path.endswith(".npy") and cv2 is None:

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define DVC_ABI_VERSION 8
+#define DVC_ABI_VERSION 9
 #define DVC_MAX_BATCH 512
 
 /* ---- status codes ---------------------------------------------------------- */
@@ -508,6 +508,51 @@ int dvc_jpeg_bound(int width, int height, int fmt, size_t* bytes);
 int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t frame_stride, int n, uint8_t* out,
                     size_t out_stride, uint32_t* sizes);
 int dvc_jpeg_sync(dvc_jpeg* h);
+
+/* ---- Motion-JPEG decoder (the read end of the same files) ----------------------- */
+/* What cap.read() does with one sample of a Motion-JPEG file (fd:86-87, of:66,
+ * of:142-143), on the GPU: baseline JPEG (SOF0, 8-bit, Huffman; one component, or
+ * three with 4:2:0 sampling; any DQT / DHT / DRI) to the bytes libjpeg's default
+ * decoder gives — slow-integer IDCT, fancy chroma upsampling, integer YCbCr to
+ * RGB — as specified in DESIGN.md "Motion-JPEG decoder". Output: packed BGR, or
+ * one byte a pixel for a single-component stream. */
+typedef struct dvc_jpegd dvc_jpegd;
+
+/* A decoder for frames up to max_width x max_height (1..65535), max_batch
+ * (0/1..DVC_MAX_BATCH) frames per device launch. hip_stream / flags as
+ * dvc_jpeg_create (DVC_FLAG_DEVICE_PTRS, DVC_FLAG_JOIN_STREAM). device < 0: a
+ * host-only handle that touches no GPU; only dvc_jpegd_set_header works on it.
+ * Replaces the cv2.VideoCapture constructions at fd:39 and of:39,121-122. */
+int dvc_jpegd_create(int max_width, int max_height, int max_batch, int device, void* hip_stream, uint32_t flags,
+                     dvc_jpegd** out);
+void dvc_jpegd_destroy(dvc_jpegd* h);
+
+/* Host only: parse SOI .. SOS from the n host bytes at hdr (a whole sample will
+ * do), build the decoding tables and quantisers for the frames that follow, and
+ * report where the entropy data starts (*header_len), the frame size and
+ * DVC_FMT_BGR or DVC_FMT_GRAY. A JPEG outside the accepted set (progressive,
+ * 12-bit, 16-bit DQT, arithmetic coding, other sampling, several scans) gives
+ * DVC_E_UNSUPPORTED; a cut or inconsistent header, or a frame larger than the
+ * handle's maximum, DVC_E_INVALID; either way the handle is unchanged. What
+ * cap.read() finds at the head of each sample (fd:86-87, of:142-143). */
+int dvc_jpegd_set_header(dvc_jpegd* h, const uint8_t* hdr, size_t n, size_t* header_len, int* width, int* height,
+                         int* fmt);
+
+/* Decode n frames of the current header: frame t's entropy data through EOI is
+ * the sizes[t] bytes at data + t*data_stride (any alignment; sizes[t] <=
+ * data_stride when n > 1), its pixels go to out + t*frame_stride in rows of
+ * `pitch` >= 3*W or W bytes, and status[t] receives 0 or a negative DVC_E_* when
+ * the frame's data is damaged (a wrong number of restart markers, an invalid
+ * code, a run past coefficient 63, data that ends early); nothing of a damaged
+ * frame is written and nothing outside a row's pixels ever is. Replaces
+ * cap.read() at fd:86-87, of:66 and of:142-143. Host pointers: returns after
+ * the frames have landed, with the first non-zero status. DVC_FLAG_DEVICE_PTRS:
+ * data, sizes, out and status are device pointers, the call is asynchronous on
+ * the handle's stream (the caller's when one was joined) and the next
+ * dvc_jpegd_sync returns the first non-zero status, once. */
+int dvc_jpegd_decode(dvc_jpegd* h, const uint8_t* data, size_t data_stride, const uint32_t* sizes, int n, uint8_t* out,
+                     size_t pitch, size_t frame_stride, int32_t* status);
+int dvc_jpegd_sync(dvc_jpegd* h);
 
 /* The Q8 fixed-point Gaussian taps OpenCV's bit-exact 8U GaussianBlur uses
  * (getGaussianKernelBitExact + error-diffusion rounding to 8 fraction bits).

@@ -1,7 +1,9 @@
 """Drop-in driver throughput (GPU box): process_single_video_fd (or _of) end to
 end as a user calls it — a 1080p Y4M (4:2:0) camera file in, the two output videos out
 (.npy streams of BGR frames, Y4M with DVC_VIDEO_SINK=y4m, or Motion-JPEG .mp4 with
-DVC_VIDEO_SINK=mjpeg), file I/O and host copies included. Prints one JSON line per run.
+DVC_VIDEO_SINK=mjpeg), file I/O and host copies included. Prints one JSON line per run
+(DVC_MJPEG_DECODE=gpu|pillow, recorded in the line, chooses how the OF driver's second
+pass reads the first pass's .mp4 files back).
   python tools/bench_dropin.py [--frames N] [--sink npy|y4m|mjpeg] [--module NAME] [--dir /tmp/x]
 """
 import argparse
@@ -52,7 +54,7 @@ def main():
     dt = time.time() - t0
     n = a.frames - 1
     print(json.dumps({"mode": f"drop-in process_single_video_{a.path}", "module": module, "source": "y4m I420 file",
-                      "sink": a.sink, "frames": n, "seconds": round(dt, 3), "fps": round(n / dt, 1),
+                      "sink": a.sink, "mjpeg_decode": os.environ.get("DVC_MJPEG_DECODE", "auto"), "frames": n, "seconds": round(dt, 3), "fps": round(n / dt, 1),
                       "Mpx_per_s": round(n * a.width * a.height / dt / 1e6, 1)}))
     shutil.rmtree(out, ignore_errors=True)
 
