@@ -985,7 +985,13 @@ int dvc_of_debug_read(dvc_of* h, int what, int level, void* dst, int* w, int* hg
         src = L.R + (size_t)(((a - what) % h->g.RS + h->g.RS) % h->g.RS) * px * 5;
         bytes = 20 * px;
     } else if (what == 2) {
-        if (level == 0 && h->g.iters < 2) return fail(DVC_E_STATE, "level 0 keeps no flow with 1 iteration");
+        // iteration `it` writes the level's flow[it & 1], except the last one of
+        // level 0 (raw bits only): flow[0] still holds iteration 0's flow unless
+        // iteration 2 has overwritten it, or nothing ever wrote it
+        const int it = h->g.iters;
+        if (level == 0 ? (it < 2 || it > 3) : it > 2)
+            return fail(DVC_E_STATE, "level %d keeps no first-iteration flow with %d iteration%s", level, it,
+                        it == 1 ? "" : "s");
         src = L.flow[0] + (size_t)(h->last_n - 1) * px * 2;
         bytes = 8 * px;
     } else {

@@ -23,11 +23,14 @@ from . import _native as N
 def derive_of_params(width: int, height: int, flow_threshold: float = 0.5, alpha_fraction: float = 0.2,
                      window_size: int = 30, morph_kernel: int = 2, quantization_level: float = 100.0,
                      flags: int = 0, direct_sums: bool = False, in_format: str = "BGR",
-                     chroma_rows: int = 0) -> N.OfParams:
+                     chroma_rows: int = 0, pyr_scale: float = 0.3, levels: int = 2, winsize: int = 9,
+                     iterations: int = 2, poly_n: int = 5, poly_sigma: float = 1.1) -> N.OfParams:
     """dvc_of_params from the reference kwargs of ``temporal_smoothing_flow``
     (of:29-31) and the arguments it hard-codes: Farneback (0.3, 2, 9, 2, 5, 1.1,
     0) at of:72-81, ``QTY_aggressive`` = 100 at of:138. ``direct_sums``: direct
-    per-pixel box sums instead of OpenCV's running sums (the default)."""
+    per-pixel box sums instead of OpenCV's running sums (the default).
+    ``pyr_scale`` ... ``poly_sigma``: the calcOpticalFlowFarneback arguments, for
+    callers other than the reference (dvc_of_create states the accepted range)."""
     p = N.OfParams()
     if direct_sums:
         flags |= N.DVC_FLAG_OF_DIRECT_SUMS
@@ -37,7 +40,8 @@ def derive_of_params(width: int, height: int, flow_threshold: float = 0.5, alpha
     p.alpha_fraction = float(alpha_fraction)
     p.window = int(window_size)
     p.morph_kernel = int(morph_kernel)
-    p.pyr_scale, p.levels, p.winsize, p.iterations, p.poly_n, p.poly_sigma = 0.3, 2, 9, 2, 5, 1.1
+    p.pyr_scale, p.levels, p.winsize = float(pyr_scale), int(levels), int(winsize)
+    p.iterations, p.poly_n, p.poly_sigma = int(iterations), int(poly_n), float(poly_sigma)
     p.flags = flags
     p.in_format = N.FORMATS[in_format]
     p.chroma_rows = int(chroma_rows)
@@ -163,7 +167,9 @@ class OFWorker:
     def debug_read(self, what: int, level: int = 0) -> np.ndarray:
         """Farneback intermediates of the last frame at a pyramid level: 0 its
         polynomial expansion R (h, w, 5), 1 the previous frame's R, 2 the flow
-        after the first iteration (h, w, 2)."""
+        after the first iteration (h, w, 2) — kept only while no later
+        iteration has reused its buffer (dvc_of_debug_read in include/dvc.h);
+        DvcError (DVC_E_STATE) otherwise."""
         w, h = ctypes.c_int(), ctypes.c_int()
         N.check(self._lib.dvc_of_debug_read(self._h, what, level, None, ctypes.byref(w), ctypes.byref(h)))
         out = np.empty((h.value, w.value, 5 if what in (0, 1) else 2), np.float32)

@@ -363,8 +363,11 @@ typedef struct dvc_of_stats {
 
 /* Create an OF feed handle on `device` (GPU constraints, DVC_E_UNSUPPORTED
  * outside them: width and height >= 8, morph_kernel 1..64 (and its halo rows
- * within the LDS at that width), poly_n 5 or 7, winsize <= 17, window
- * 1..255, <= 6 pyramid levels). Replaces the per-video setup at
+ * within the LDS at that width), poly_n 5 or 7, winsize 1..17, window
+ * 1..255, <= 6 pyramid levels, pyramid smoothing kernels of <= 63 taps;
+ * DVC_E_INVALID for iterations < 1, levels < 0 or pyr_scale outside (0, 1)).
+ * An even winsize is OpenCV's: the box is 2 (winsize / 2) + 1 wide, the sums
+ * scaled by 1 / winsize^2. Replaces the per-video setup at
  * of:38-62. The gray/pyramid, flow and vote/morphology/output stages run on
  * three internal streams with two batches' rings in flight; `hip_stream`
  * (hipStream_t or NULL) is joined as in dvc_fd_create. Device-pointer steps
@@ -434,8 +437,10 @@ void dvc_of_destroy(dvc_of* h);
 /* Parity/debug readback of Farneback intermediates of the LAST stepped frame at
  * pyramid level `level` (host memory): what 0 = its polynomial expansion R
  * (h_k*w_k*5 floats), 1 = the previous frame's R, 2 = the flow after the first
- * iteration (h_k*w_k*2 floats; needs iterations >= 2 or level > 0). *w, *h
- * (nullable) receive the level size; dst may be NULL to query it. */
+ * iteration (h_k*w_k*2 floats). That flow is kept only until a later iteration
+ * reuses its buffer: at a level > 0 with iterations <= 2, at level 0 with
+ * iterations 2 or 3 (its last iteration stores no flow); DVC_E_STATE otherwise.
+ * *w, *h (nullable) receive the level size; dst may be NULL to query it. */
 int dvc_of_debug_read(dvc_of* h, int what, int level, void* host_dst, int* w, int* hgt);
 
 /* compress_with_motion for one frame with an arbitrary mask (of:141-185, e.g.

@@ -433,15 +433,18 @@ class OfParams(ctypes.Structure):
 
 
 def of_params(width, height, flow_threshold=0.5, alpha_fraction=0.2, window_size=30, morph_kernel=2,
-              quant=100.0, direct_sums=False) -> OfParams:
-    """motion_compression_opt.py:29-31 kwargs + the hard-coded Farneback arguments (of:72-81).
+              quant=100.0, direct_sums=False, pyr_scale=0.3, levels=2, winsize=9, iterations=2, poly_n=5,
+              poly_sigma=1.1) -> OfParams:
+    """motion_compression_opt.py:29-31 kwargs + the Farneback arguments, by default the ones the
+    reference hard-codes (of:72-81).
     ``direct_sums``: direct per-pixel box sums instead of OpenCV's running sums."""
     p = OfParams()
     p.flags = 0x10 if direct_sums else 0
     p.width, p.height = int(width), int(height)
     p.flow_threshold, p.quant = float(flow_threshold), float(quant)
     p.alpha_fraction, p.window, p.morph_kernel = float(alpha_fraction), int(window_size), int(morph_kernel)
-    p.pyr_scale, p.levels, p.winsize, p.iterations, p.poly_n, p.poly_sigma = 0.3, 2, 9, 2, 5, 1.1
+    p.pyr_scale, p.levels, p.winsize = float(pyr_scale), int(levels), int(winsize)
+    p.iterations, p.poly_n, p.poly_sigma = int(iterations), int(poly_n), float(poly_sigma)
     return p
 
 
@@ -473,6 +476,7 @@ def _of_lib():
         L.oc_update_flow_box.argtypes = [fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp]
         L.oc_update_flow_box_sliding.argtypes = [fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp]
         L.oc_of_set_sliding.argtypes = [ctypes.c_int]
+        L.oc_resize_linear_f32.argtypes = [fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, ctypes.c_int, ctypes.c_int]
         L._of_ready = True
     return L
 
@@ -516,6 +520,16 @@ def fb_iteration(R0: np.ndarray, R1: np.ndarray, flow: np.ndarray, winsize=9, sl
     _of_lib().oc_update_matrices(_fp(R0), _fp(R1), _fp(f), w, h, _fp(M), 0, h)
     (_of_lib().oc_update_flow_box_sliding if sliding else _of_lib().oc_update_flow_box)(_fp(M), w, h, winsize, _fp(f))
     return f
+
+
+def fb_upsample(flow: np.ndarray, w: int, h: int, pyr_scale=0.3) -> np.ndarray:
+    """A coarser level's final flow as the next finer (w x h) level starts from it:
+    INTER_LINEAR resize, times (float)(1 / pyr_scale) (oc_farneback)."""
+    flow = np.ascontiguousarray(flow, np.float32)
+    sh, sw = flow.shape[:2]
+    out = np.empty((int(h), int(w), 2), np.float32)
+    _of_lib().oc_resize_linear_f32(_fp(flow), sw, sh, 2, _fp(out), int(w), int(h))
+    return out * np.float32(1.0 / pyr_scale)
 
 
 def morph_close_open(m: np.ndarray, k: int = 2) -> np.ndarray:

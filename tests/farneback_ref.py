@@ -18,6 +18,7 @@ encoded here with a comment naming the place in OpenCV 4.x
 """
 from __future__ import annotations
 
+import dataclasses
 import functools
 from collections import deque
 
@@ -32,6 +33,26 @@ ITERATIONS = 2
 POLY_N = 5             # window radius: (2 * 5 + 1)^2 = 11 x 11
 POLY_SIGMA = 1.1
 BORDER = (0.14, 0.14, 0.4472, 0.4472, 0.4472)   # FarnebackUpdateMatrices: `static const float border[]`
+
+
+@dataclasses.dataclass(frozen=True)
+class Params:
+    """The six calcOpticalFlowFarneback arguments; the defaults are the module
+    constants above (what the reference passes). Frozen and hashable: a key of
+    :func:`flow_case`'s cache. ``kwargs()`` are the keywords OFWorker, OracleOF
+    and oracle.farneback take."""
+    pyr_scale: float = PYR_SCALE
+    levels: int = MAX_LEVELS
+    winsize: int = WINSIZE
+    iterations: int = ITERATIONS
+    poly_n: int = POLY_N
+    poly_sigma: float = POLY_SIGMA
+
+    def kwargs(self) -> dict:
+        return dataclasses.asdict(self)
+
+
+DEFAULT = Params()
 
 # Shapes of the comparisons (W, H): one level; L = 1 with an odd coarse level;
 # L = 2 with level sizes 109 x 107 and 33 x 32; the GPU adds a partial strip.
@@ -69,6 +90,11 @@ SHAPES_GPU = ((96, 64), (136, 72), (124, 108), (364, 356))
 #
 # The polynomial coefficients have a value scale of ~30 (gray levels per
 # pixel); the flows are in pixels.
+#
+# The figures above are the reference's arguments (0.3, 2, 9, 2, 5, 1.1). The
+# other argument sets dvc_of_create accepts have one row each in PARAM_SETS
+# further down (it needs Params): measured error, 8 x tolerance and the margin
+# to the nearest accepted neighbour, and the answer on winsize 1 in words.
 POLY_MEASURED = 5.5e-5        # 5.40e-5 at 364 x 356
 POLY_TOL = 8 * POLY_MEASURED
 POLY_MUTATION_MIN = 0.27
@@ -86,11 +112,11 @@ MASK_EXCUSED_SHARE = 1e-3
 
 
 # ------------------------------------------------------------------ pyramid --
-def levels(W: int, H: int) -> int:
+def levels(W: int, H: int, p: Params = DEFAULT) -> int:
     """Number of extra pyramid levels: scale *= pyr_scale while both sides stay >= min_size."""
     scale, k = 1.0, 0
-    while k < MAX_LEVELS:
-        scale *= PYR_SCALE
+    while k < p.levels:
+        scale *= p.pyr_scale
         if W * scale < MIN_SIZE or H * scale < MIN_SIZE:
             break
         k += 1
@@ -128,46 +154,47 @@ def resize_linear(img: np.ndarray, dw: int, dh: int) -> np.ndarray:
     return rows[:, x0] * (1 - ax)[None] + rows[:, x1] * ax[None]
 
 
-def level_size(W: int, H: int, k: int):
-    scale = PYR_SCALE ** k
+def level_size(W: int, H: int, k: int, p: Params = DEFAULT):
+    scale = p.pyr_scale ** k
     return int(np.rint(W * scale)), int(np.rint(H * scale))
 
 
-def level_image(gray: np.ndarray, k: int) -> np.ndarray:
+def level_image(gray: np.ndarray, k: int, p: Params = DEFAULT) -> np.ndarray:
     """Level k of the pyramid: the full-size image blurred with sigma =
     (1 / scale - 1) / 2 (REFLECT_101 = scipy's 'mirror'), then resized."""
     H, W = gray.shape
-    sigma = (1.0 / PYR_SCALE ** k - 1) * 0.5
+    sigma = (1.0 / p.pyr_scale ** k - 1) * 0.5
     ksize = max(int(np.rint(sigma * 5)) | 1, 3)
     taps = gauss_taps(ksize, sigma)
     img = gray.astype(np.float64)
     img = ndimage.correlate1d(img, taps, axis=1, mode="mirror")
     img = ndimage.correlate1d(img, taps, axis=0, mode="mirror")
-    w, h = level_size(W, H, k)
+    w, h = level_size(W, H, k, p)
     return resize_linear(img, w, h)
 
 
 # ------------------------------------------------------ polynomial expansion --
-def _poly_basis():
+def _poly_basis(p: Params = DEFAULT):
     """Window offsets, applicability and the basis (1, x, y, x^2, y^2, xy)."""
-    o = np.arange(-POLY_N, POLY_N + 1, dtype=np.float64)
-    g = np.exp(-o * o / (2 * POLY_SIGMA ** 2))
+    o = np.arange(-p.poly_n, p.poly_n + 1, dtype=np.float64)
+    g = np.exp(-o * o / (2 * p.poly_sigma ** 2))
     return o, g / g.sum()
 
 
-def polyexp(I: np.ndarray) -> np.ndarray:
+def polyexp(I: np.ndarray, p: Params = DEFAULT) -> np.ndarray:
     """Gaussian-weighted least-squares fit of c + bx x + by y + axx x^2 +
-    ayy y^2 + axy xy over the 11 x 11 window of every pixel (replicated
+    ayy y^2 + axy xy over the (2 poly_n + 1)^2 window (11 x 11 by default) of
+    every pixel (replicated
     borders): r = (B^T W B)^-1 B^T W f with the full 6 x 6 Gram matrix.
     Returns (h, w, 5): by, bx, ayy, axx, axy (the project's channel order)."""
-    o, g = _poly_basis()
+    o, g = _poly_basis(p)
     I = np.asarray(I, dtype=np.float64)
     px = [np.ones_like(o), o, o * o]
     # basis functions as (power of x, power of y)
     basis = [(0, 0), (1, 0), (0, 1), (2, 0), (0, 2), (1, 1)]
     Y, X = np.meshgrid(o, o, indexing="ij")
     Wt = np.outer(g, g)
-    Bm = np.stack([X ** a * Y ** b for a, b in basis], axis=-1).reshape(-1, 6)     # (121, 6)
+    Bm = np.stack([X ** a * Y ** b for a, b in basis], axis=-1).reshape(-1, 6)     # ((2 n + 1)^2, 6)
     G = Bm.T @ (Wt.reshape(-1, 1) * Bm)                                             # B^T W B
     # B^T W f: the weight g(x) g(y) x^a y^b separates into a row and a column pass
     moments = np.empty(I.shape + (6,))
@@ -178,10 +205,11 @@ def polyexp(I: np.ndarray) -> np.ndarray:
     return np.stack([r[..., 2], r[..., 1], r[..., 4], r[..., 3], r[..., 5]], axis=-1)
 
 
-def polyexp_pixel(I: np.ndarray, x: int, y: int) -> np.ndarray:
+def polyexp_pixel(I: np.ndarray, x: int, y: int, p: Params = DEFAULT) -> np.ndarray:
     """The same fit at one pixel by weighted ``lstsq`` over the explicit 121
-    samples — the definition itself, used to check :func:`polyexp`."""
-    o, g = _poly_basis()
+    (at poly_n 7: 225) samples — the definition itself, used to check
+    :func:`polyexp`."""
+    o, g = _poly_basis(p)
     H, W = I.shape
     ys = np.clip(y + o.astype(int), 0, H - 1)
     xs = np.clip(x + o.astype(int), 0, W - 1)
@@ -224,11 +252,13 @@ def displaced_inside(flow: np.ndarray) -> np.ndarray:
     return (x0 >= 0) & (x0 < W - 1) & (y0 >= 0) & (y0 < H - 1)
 
 
-def iteration(R0: np.ndarray, R1: np.ndarray, flow: np.ndarray) -> np.ndarray:
+def iteration(R0: np.ndarray, R1: np.ndarray, flow: np.ndarray, p: Params = DEFAULT,
+              running_sums: bool = False) -> np.ndarray:
     """One displacement update. With A = [[axx, axy/2], [axy/2, ayy]] and
     b = (bx, by) of each frame: A = (A0 + A1(x + d)) / 2, db = (b0 - b1(x + d))
-    / 2 + A d, G = A^T A and h = A^T db averaged over the 9 x 9 box
-    (replicated borders), d = adj(G) h / (det G + 1e-3)."""
+    / 2 + A d, G = A^T A and h = A^T db averaged over the winsize x winsize box
+    (9 x 9 by default; replicated borders), d = adj(G) h / (det G + 1e-3).
+    ``running_sums`` matters at winsize 1 only (see below)."""
     R0, R1 = np.asarray(R0, np.float64), np.asarray(R1, np.float64)
     flow = np.asarray(flow, np.float64)
     H, W = R0.shape[:2]
@@ -247,8 +277,23 @@ def iteration(R0: np.ndarray, R1: np.ndarray, flow: np.ndarray) -> np.ndarray:
     A, db = A * s[..., None, None], db * s[..., None]
     G = np.einsum("...ki,...kj->...ij", A, A)
     h = np.einsum("...ki,...k->...i", A, db)
-    G = ndimage.uniform_filter(G, size=(WINSIZE, WINSIZE, 1, 1), mode="nearest")
-    h = ndimage.uniform_filter(h, size=(WINSIZE, WINSIZE, 1), mode="nearest")
+    # OpenCV's choice for an even winsize (FarnebackUpdateFlow_Blur: `int m =
+    # block_size/2`, `double scale = 1./(block_size*block_size)`): the sums run
+    # over the odd window 2 (winsize // 2) + 1, yet are scaled by 1 / winsize^2.
+    box = 2 * (p.winsize // 2) + 1
+    rescale = (box * box) / float(p.winsize * p.winsize)
+    G = ndimage.uniform_filter(G, size=(box, box, 1, 1), mode="nearest") * rescale
+    h = ndimage.uniform_filter(h, size=(box, box, 1), mode="nearest") * rescale
+    if running_sums and box == 1:
+        # OpenCV's choice at winsize 1 (FarnebackUpdateFlow_Blur): it keeps
+        # running sums, and starts the vertical one with `srow0[x]*(m+2)` plus
+        # rows 1 ... m - 1 — the 2 m + 1 rows of the window above row 0. At m = 0
+        # that window has one row, the start puts two, and the surplus copy of
+        # row 0 never leaves the sum; the horizontal sum does the same with
+        # column 0. What OpenCV solves at (y, x) is therefore the sum over (y, x),
+        # (0, x), (y, 0) and (0, 0) — in exact arithmetic, not by rounding.
+        G = G + G[:1] + G[:, :1] + G[:1, :1]
+        h = h + h[:1] + h[:, :1] + h[:1, :1]
     # FarnebackUpdateFlow_Blur regularises the determinant, not the diagonal
     idet = 1.0 / (G[..., 0, 0] * G[..., 1, 1] - G[..., 0, 1] * G[..., 1, 0] + 1e-3)
     dx = (G[..., 1, 1] * h[..., 0] - G[..., 0, 1] * h[..., 1]) * idet
@@ -256,19 +301,19 @@ def iteration(R0: np.ndarray, R1: np.ndarray, flow: np.ndarray) -> np.ndarray:
     return np.stack([dx, dy], axis=-1)
 
 
-def farneback(g0: np.ndarray, g1: np.ndarray, polys=None) -> np.ndarray:
+def farneback(g0: np.ndarray, g1: np.ndarray, polys=None, p: Params = DEFAULT, running_sums: bool = False) -> np.ndarray:
     """Coarse to fine; ``polys(img_index, k)`` may supply cached expansions."""
     H, W = g0.shape
     flow = None
-    for k in range(levels(W, H), -1, -1):
+    for k in range(levels(W, H, p), -1, -1):
         if polys is None:
-            R0, R1 = polyexp(level_image(g0, k)), polyexp(level_image(g1, k))
+            R0, R1 = polyexp(level_image(g0, k, p), p), polyexp(level_image(g1, k, p), p)
         else:
             R0, R1 = polys(0, k), polys(1, k)
         h, w = R0.shape[:2]
-        flow = np.zeros((h, w, 2)) if flow is None else resize_linear(flow, w, h) * (1.0 / PYR_SCALE)
-        for _ in range(ITERATIONS):
-            flow = iteration(R0, R1, flow)
+        flow = np.zeros((h, w, 2)) if flow is None else resize_linear(flow, w, h) * (1.0 / p.pyr_scale)
+        for _ in range(p.iterations):
+            flow = iteration(R0, R1, flow, p, running_sums)
     return flow
 
 
@@ -315,15 +360,123 @@ FLOW_CASES = {
 
 
 @functools.lru_cache(maxsize=None)
-def flow_case(W: int, H: int, dx: float, dy: float):
+def flow_case(W: int, H: int, dx: float, dy: float, p: Params = DEFAULT):
     """(g0, g1, {(frame, level): polyexp}, flow) of one textured pair, computed
     once a session and shared read-only by every test that needs it."""
     g0, g1 = textured_pair(W, H, dx, dy, seed=W + H)
-    polys = {(i, k): polyexp(level_image(g, k)) for k in range(levels(W, H) + 1) for i, g in enumerate((g0, g1))}
-    flow = farneback(g0, g1, polys=lambda i, k: polys[i, k])
+    polys = {(i, k): polyexp(level_image(g, k, p), p) for k in range(levels(W, H, p) + 1)
+             for i, g in enumerate((g0, g1))}
+    flow = farneback(g0, g1, polys=lambda i, k: polys[i, k], p=p)
     for a in (g0, g1, flow, *polys.values()):
         a.setflags(write=False)
     return g0, g1, polys, flow
+
+
+# ------------------------------------------------- non-default parameter sets --
+@dataclasses.dataclass(frozen=True)
+class ParamSet:
+    """One point of the parameter space dvc_of_create accepts, with the inputs
+    it is checked on and the figures measured there (the table below)."""
+    p: Params
+    neighbour: Params            # the nearest accepted set its flow must differ from
+    cases: tuple                 # (W, H, dx, dy) textured pairs: CPU and GPU float64 comparisons
+    poly_measured: float
+    iter_measured: float
+    flow_measured: float
+    margin: float                # smallest max |flow(p) - flow(neighbour)| over the cases, float64
+
+    @property
+    def poly_tol(self):
+        return 8 * self.poly_measured
+
+    @property
+    def iter_tol(self):
+        return 8 * self.iter_measured
+
+    @property
+    def flow_tol(self):
+        return 8 * self.flow_measured
+
+
+# The median error of the float64 flow against the true translation stays under
+# FLOW_TRUTH_MEDIAN on every case below (0.015 ... 0.044 px; the displacements
+# are chosen for that: at (-2.3, 1.6) pyr_scale 0.5 measures 0.052), and no
+# pixel of a case lies within its tolerance of the 0.5 threshold.
+#
+# winsize 1 is not in the table; it has constants of its own. The question was
+# why the oracle's running sums and its direct sums differ by 7.7 px there, and
+# from the float64 definition by as much. Answer: neither rounding nor an
+# oracle defect. In exact arithmetic OpenCV's running sums do not compute the
+# one-pixel box at m = 0 (the start `srow0[x]*(m+2)` of FarnebackUpdateFlow_Blur
+# assumes m >= 1, see iteration()): they solve G and h summed over (y, x),
+# (0, x), (y, 0) and (0, 0). With that start written into iteration(...,
+# running_sums=True) the oracle's running sums agree with float64 to 1.4e-5
+# (one iteration) and 9.8e-5 px (final flow, 96 x 64, (-1.3, 0.9)): the same
+# chain as any other winsize, the larger figure coming from the update itself.
+# The direct sums do compute the one-pixel box, and there G = A^T A has det G =
+# det(A)^2: on that frame 22 % of the pixels have det G below the 1e-3
+# regulariser (median 0.025), so the update amplifies float32 rounding. Oracle
+# direct sums vs float64: 2.9e-4 (iteration) and 8.1e-4 px (flow), the worst
+# pixel at det G = 5.9e-6; restricted to det G >= 0.1 the iteration differs by
+# 4.7e-6, to det G >= 1 by 6.2e-7 — ill-conditioning, not a defect. Neither
+# order estimates the translation (median error 0.25 and 0.11 px), so winsize 1
+# is held to float64 in both orders but exempt from FLOW_TRUTH_MEDIAN.
+W1_CASE = (96, 64, -1.3, 0.9)
+W1_RUNNING_ITER_MEASURED = 1.4e-5
+W1_RUNNING_FLOW_MEASURED = 9.8e-5      # tolerance 7.9e-4; margin to the default's flow 5.0 px
+W1_DIRECT_ITER_MEASURED = 2.9e-4
+W1_DIRECT_FLOW_MEASURED = 8.1e-4       # tolerance 6.5e-3; margin to the default's flow 19.9 px
+W1_MARGIN = 5.0
+
+_C124, _C96, _C136, _C264, _C333 = (124, 108, 1.3, -0.9), (96, 64, -1.3, 0.9), (136, 76, 1.1, -0.8), \
+    (264, 260, -1.7, 1.2), (333, 185, 1.4, -0.9)
+_P7 = Params(poly_n=7, poly_sigma=1.5)
+_ALL = Params(0.5, 3, 13, 3, 7, 1.5)
+
+PARAM_SETS = {
+    # name: parameters, neighbour, cases, then the largest |oracle - this module| over the cases and both
+    # box orders for the expansion (every level), the coarsest level's first iteration and the final flow
+    # [px]; each tolerance is 8 x its figure (flow tolerance in the comment); last the margin: the smallest
+    # max |flow - the neighbour's flow| over the cases in float64, which must be >= 10 x the flow tolerance
+    # (test_param_set_discriminates). Measured on the CPU by tests/test_of_oracle.py, which prints each.
+    "poly7": ParamSet(_P7, Params(poly_sigma=1.5), (_C124, _C333),
+                      2.6e-5, 1.3e-6, 7.8e-6, 0.0129),          # tol 6.2e-5 px; vs poly_n 5 at sigma 1.5
+    "winsize5": ParamSet(Params(winsize=5), DEFAULT, (_C124,),
+                         2.0e-5, 2.1e-6, 1.3e-5, 2.24),         # tol 1.0e-4 px
+    "winsize8": ParamSet(Params(winsize=8), DEFAULT, (_C124,),
+                         2.0e-5, 5.9e-7, 5.0e-6, 0.314),        # tol 4.0e-5 px; vs 9: same window, scale 1/64
+    "winsize13": ParamSet(Params(winsize=13), DEFAULT, (_C124,),
+                          2.0e-5, 3.7e-7, 2.8e-6, 1.15),        # tol 2.2e-5 px
+    "winsize17": ParamSet(Params(winsize=17), Params(winsize=15), (_C124, _C136),
+                          2.0e-5, 1.9e-6, 2.6e-6, 0.219),       # tol 2.1e-5 px; vs winsize 15
+    "iterations1": ParamSet(Params(iterations=1), DEFAULT, (_C124, _C96),
+                            2.0e-5, 3.7e-6, 4.7e-6, 0.612),     # tol 3.8e-5 px
+    "iterations3": ParamSet(Params(iterations=3), DEFAULT, (_C124,),
+                            2.0e-5, 6.1e-7, 4.6e-6, 0.183),     # tol 3.7e-5 px
+    "pyr0.5_levels3": ParamSet(Params(pyr_scale=0.5, levels=3), DEFAULT, (_C264,),
+                               1.5e-5, 4.5e-7, 1.3e-5, 0.132),  # tol 1.0e-4 px; L = 3: 132x130, 66x65, 33x32
+    "pyr0.8_levels5": ParamSet(Params(pyr_scale=0.8, levels=5), DEFAULT, (_C124,),
+                               2.8e-5, 7.7e-7, 4.8e-6, 0.211),  # tol 3.8e-5 px; L = 5, coarsest 41x35
+    "levels0": ParamSet(Params(levels=0), DEFAULT, (_C124,),
+                        1.3e-5, 6.4e-6, 5.2e-6, 0.313),         # tol 4.2e-5 px
+    "all": ParamSet(_ALL, DEFAULT, (_C264,),
+                    1.3e-5, 5.2e-7, 4.3e-6, 1.52),              # tol 3.4e-5 px
+}
+
+
+@functools.lru_cache(maxsize=None)
+def winsize1_case():
+    """(g0, g1, {frame: polyexp}, flow as OpenCV's running sums give it, flow by
+    the one-pixel box) of W1_CASE in float64, read-only."""
+    W, H, dx, dy = W1_CASE
+    p = Params(winsize=1)
+    assert levels(W, H, p) == 0
+    g0, g1 = textured_pair(W, H, dx, dy, seed=W + H)
+    polys = {i: polyexp(level_image(g, 0, p), p) for i, g in enumerate((g0, g1))}
+    flows = [farneback(g0, g1, polys=lambda i, k: polys[i], p=p, running_sums=r) for r in (True, False)]
+    for a in (g0, g1, *flows, *polys.values()):
+        a.setflags(write=False)
+    return g0, g1, polys, flows[0], flows[1]
 
 
 # --------------------------------------------- vote, morphology, rectangles --

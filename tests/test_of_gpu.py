@@ -18,19 +18,22 @@ def _first_diff(g, r):
     return f"{len(d)} differ, first {d[:4].tolist()}"
 
 
-def _run_pair(dvc_amd, oracle, frames, batch=0, **kw):
-    """Per-frame (batch=0) or batched GPU run vs the oracle; returns GPU stats."""
-    H, W = frames.shape[1:3]
+def _run_pair(dvc_amd, oracle, frames, batch=0, ref_frames=None, **kw):
+    """Per-frame (batch=0) or batched GPU run vs the oracle; returns GPU stats.
+    ``ref_frames``: the BGR frames the oracle gets where ``frames`` are 4:2:0."""
+    rframes = frames if ref_frames is None else ref_frames
+    H, W = rframes.shape[1:3]
     okw = {k: v for k, v in kw.items()
-           if k in ("flow_threshold", "alpha_fraction", "window_size", "morph_kernel", "direct_sums")}
+           if k in ("flow_threshold", "alpha_fraction", "window_size", "morph_kernel", "direct_sums", "pyr_scale",
+                    "levels", "winsize", "iterations", "poly_n", "poly_sigma")}
     gpu = dvc_amd.OFWorker(W, H, device=0, keep_planes=True, max_batch=max(batch, 1), **kw)
     ref = oracle.OracleOF(W, H, **okw)
     gpu.prime(frames[0])
-    ref.prime(frames[0])
+    ref.prime(rframes[0])
     motion = comps = static = 0
     rmasks, rcps = [], []
     for t in range(1, len(frames)):
-        rmask, rcp, rflow = ref.step(frames[t])
+        rmask, rcp, rflow = ref.step(rframes[t])
         rmasks.append(rmask)
         rcps.append(rcp)
         raw = ref.plane(0)

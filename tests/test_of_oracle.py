@@ -44,6 +44,34 @@ def test_polyexp_equals_pointwise_lstsq():
         assert np.abs(R[y, x] - F.polyexp_pixel(I, x, y)).max() < 1e-9, (x, y)
 
 
+def test_polyexp_poly_n7_equals_pointwise_lstsq():
+    """The same at poly_n 7, sigma 1.5: the 15 x 15 window, 225 samples."""
+    p = F.Params(poly_n=7, poly_sigma=1.5)
+    rng = np.random.default_rng(6)
+    I = rng.uniform(0, 255, (23, 31))
+    R = F.polyexp(I, p)
+    for x, y in [(0, 0), (30, 0), (0, 22), (30, 22), (5, 11), (15, 3), (26, 18), (15, 11)]:
+        assert np.abs(R[y, x] - F.polyexp_pixel(I, x, y, p)).max() < 1e-9, (x, y)
+    assert np.abs(R - F.polyexp(I)).max() > 1.0, "another window, another fit"
+
+
+@pytest.mark.parametrize("W,H,scale,levels,sizes", [
+    (264, 260, 0.5, 3, [(264, 260), (132, 130), (66, 65), (33, 32)]),     # 32.5 rounds to even, as lrint does
+    (264, 260, 0.5, 5, [(264, 260), (132, 130), (66, 65), (33, 32)]),     # min_size 32 ends it
+    (124, 108, 0.8, 5, [(124, 108), (99, 86), (79, 69), (63, 55), (51, 44), (41, 35)]),
+    (124, 108, 0.3, 0, [(124, 108)]),
+    (124, 108, 0.9, 6, [(124, 108), (112, 97), (100, 87), (90, 79), (81, 71), (73, 64), (66, 57)]),
+])
+def test_levels_and_sizes_other_scales(oracle_lib, W, H, scale, levels, sizes):
+    p = F.Params(pyr_scale=scale, levels=levels)
+    L = len(sizes) - 1
+    assert F.levels(W, H, p) == L == oracle_lib._of_lib().oc_fb_levels(W, H, scale, levels)
+    assert [F.level_size(W, H, k, p) for k in range(L + 1)] == sizes
+    g = np.zeros((H, W), np.uint8)
+    for k in range(L + 1):
+        assert oracle_lib.fb_level_poly(g, k, pyr_scale=scale).shape == sizes[k][::-1] + (5,)
+
+
 def test_levels_and_sizes(oracle_lib):
     for (W, H), L, sizes in [((96, 64), 0, [(96, 64)]), ((136, 72), 0, [(136, 72)]),
                              ((124, 108), 1, [(124, 108), (37, 32)]),
@@ -149,6 +177,118 @@ def test_tolerances_discriminate():
                                     (F.FLOW_MEASURED, F.FLOW_TOL, F.FLOW_MUTATION_MIN)):
         assert measured > 0 and tol == 8 * measured
         assert tol < mutation / 10
+
+
+# ------------------------------------------------- non-default parameter sets --
+def _oracle_kw(p):
+    return dict(pyr_scale=p.pyr_scale, poly_n=p.poly_n, poly_sigma=p.poly_sigma)
+
+
+def measure_param_set(oracle_lib, ps):
+    """Every oracle-vs-float64 figure of one parameter set over its cases: the
+    expansion at every level, the coarsest level's first iteration and the
+    final flow (both box orders each), the share of pixels near the threshold,
+    the median error against the true translation, and the float64 distance to
+    the neighbouring set."""
+    p = ps.p
+    out = dict(poly=0.0, iter=0.0, flow=0.0, near=0.0, median=0.0, margin=np.inf, mask_ok=True)
+    for W, H, dx, dy in ps.cases:
+        g0, g1, polys, want = F.flow_case(W, H, dx, dy, p)
+        L = F.levels(W, H, p)
+        for k in range(L + 1):
+            for i, g in enumerate((g0, g1)):
+                got = oracle_lib.fb_level_poly(g, k, **_oracle_kw(p))
+                assert got.shape == polys[i, k].shape == F.level_size(W, H, k, p)[::-1] + (5,), (k, got.shape)
+                out["poly"] = max(out["poly"], float(np.abs(got - polys[i, k]).max()))
+        R0, R1 = (oracle_lib.fb_level_poly(g, L, **_oracle_kw(p)) for g in (g0, g1))
+        zero = np.zeros(R0.shape[:2] + (2,), np.float32)
+        want_it = F.iteration(polys[0, L], polys[1, L], zero, p)
+        mag = np.hypot(want[..., 0], want[..., 1])
+        for sliding in (True, False):
+            got = oracle_lib.fb_iteration(R0, R1, zero, winsize=p.winsize, sliding=sliding)
+            out["iter"] = max(out["iter"], float(np.abs(got - want_it).max()))
+            got = oracle_lib.farneback(g0, g1, sliding=sliding, **p.kwargs())
+            out["flow"] = max(out["flow"], float(np.abs(got - want).max()))
+            differ = (np.hypot(got[..., 0], got[..., 1]) > F.FLOW_THRESHOLD) != (mag > F.FLOW_THRESHOLD)
+            out["mask_ok"] &= not (differ & (np.abs(mag - F.FLOW_THRESHOLD) > ps.flow_tol)).any()
+        out["near"] = max(out["near"], float((np.abs(mag - F.FLOW_THRESHOLD) <= ps.flow_tol).mean()))
+        err = want[16:-16, 16:-16] - np.array([dx, dy])
+        out["median"] = max(out["median"], float(np.median(np.hypot(err[..., 0], err[..., 1]))))
+        other = F.flow_case(W, H, dx, dy, ps.neighbour)[3]
+        out["margin"] = min(out["margin"], float(np.abs(want - other).max()))
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(F.PARAM_SETS))
+def test_param_set_vs_float64(oracle_lib, name):
+    """The oracle at a non-default point of the space dvc_of_create accepts:
+    expansion, first iteration and final flow against float64, both box orders,
+    within 8 x the error measured for this set (the table of farneback_ref.py);
+    the raw mask may differ only within that tolerance of the threshold, on
+    under 0.1 % of the pixels."""
+    ps = F.PARAM_SETS[name]
+    m = measure_param_set(oracle_lib, ps)
+    _report(f"{name} polyexp", m["poly"], ps.poly_tol)
+    _report(f"{name} iteration", m["iter"], ps.iter_tol)
+    _report(f"{name} flow", m["flow"], ps.flow_tol)
+    print(f"{name}: near the threshold {m['near']:.2e}, median error against the truth {m['median']:.4f} px")
+    assert m["poly"] <= ps.poly_tol and m["iter"] <= ps.iter_tol and m["flow"] <= ps.flow_tol
+    assert m["near"] < F.MASK_EXCUSED_SHARE and m["mask_ok"]
+    assert m["median"] < F.FLOW_TRUTH_MEDIAN
+
+
+@pytest.mark.parametrize("name", sorted(F.PARAM_SETS))
+def test_param_set_discriminates(name):
+    """No mutation needed: the float64 flow of the set differs from the float64
+    flow of its nearest accepted neighbour (the default, or the adjacent value)
+    by at least 10 x the set's tolerance on every case, so code that ignored
+    the parameter — or scaled an even box by its odd window — cannot pass."""
+    ps = F.PARAM_SETS[name]
+    assert ps.neighbour != ps.p
+    for W, H, dx, dy in ps.cases:
+        a, b = F.flow_case(W, H, dx, dy, ps.p)[3], F.flow_case(W, H, dx, dy, ps.neighbour)[3]
+        margin = float(np.abs(a - b).max())
+        print(f"{name} {W}x{H}: max |flow - neighbour's| {margin:.3e} (10 x tolerance {10 * ps.flow_tol:.3e})")
+        assert margin >= 10 * ps.flow_tol
+        assert margin >= 0.999 * ps.margin, "the table's margin is the smallest over the cases"
+    for measured, tol in ((ps.poly_measured, ps.poly_tol), (ps.iter_measured, ps.iter_tol),
+                          (ps.flow_measured, ps.flow_tol)):
+        assert measured > 0 and tol == 8 * measured
+
+
+def test_winsize1_vs_float64(oracle_lib):
+    """winsize 1 (m = 0), each box order against what it computes in exact
+    arithmetic: the running sums against float64 with OpenCV's start of the
+    sums written in (the pixel plus row 0, column 0 and the corner), the direct
+    sums against the one-pixel box. The two differ by pixels from each other —
+    by definition, not by rounding (the comment above farneback_ref.W1_CASE)."""
+    W, H, dx, dy = F.W1_CASE
+    p = F.Params(winsize=1)
+    g0, g1, polys, running, direct = F.winsize1_case()
+    R0, R1 = polys[0].astype(np.float32), polys[1].astype(np.float32)
+    zero = np.zeros((H, W, 2), np.float32)
+    for sliding, want, it_m, flow_m in ((True, running, F.W1_RUNNING_ITER_MEASURED, F.W1_RUNNING_FLOW_MEASURED),
+                                        (False, direct, F.W1_DIRECT_ITER_MEASURED, F.W1_DIRECT_FLOW_MEASURED)):
+        name = "winsize1 " + ("running sums" if sliding else "direct sums")
+        got = oracle_lib.fb_iteration(R0, R1, zero, winsize=1, sliding=sliding)
+        err = float(np.abs(got - F.iteration(R0, R1, zero, p, running_sums=sliding)).max())
+        _report(name + " iteration", err, 8 * it_m)
+        assert err <= 8 * it_m
+        got = oracle_lib.farneback(g0, g1, sliding=sliding, **p.kwargs())
+        err = float(np.abs(got - want).max())
+        _report(name + " flow", err, 8 * flow_m)
+        assert err <= 8 * flow_m
+        mag = np.hypot(want[..., 0], want[..., 1])
+        near = np.abs(mag - F.FLOW_THRESHOLD) <= 8 * flow_m
+        differ = (np.hypot(got[..., 0], got[..., 1]) > F.FLOW_THRESHOLD) != (mag > F.FLOW_THRESHOLD)
+        print(f"{name}: near the threshold {near.mean():.2e}")
+        assert not (differ & ~near).any()
+        margin = float(np.abs(want - F.flow_case(W, H, dx, dy)[3]).max())
+        print(f"{name}: max |flow - the default's| {margin:.3e}")
+        assert margin >= F.W1_MARGIN >= 10 * 8 * flow_m
+    between = float(np.abs(running - direct).max())
+    print(f"winsize1: running vs direct sums in float64 {between:.3e} px")
+    assert between > 1.0
 
 
 # --------------------------------------------------------- ellipse, close/open --
