@@ -14,3 +14,5 @@ __version__ = "0.1.0"
 from . import _native  # noqa: F401  (loading is lazy; no CPU fallback)
 from .fd import FDWorker, derive_params  # noqa: F401
 from .of import OFWorker, derive_of_params  # noqa: F401,E402
+from ._native import QualityMeter  # noqa: F401,E402
+from .quality import compare_videos  # noqa: F401,E402

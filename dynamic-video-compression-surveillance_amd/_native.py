@@ -17,9 +17,11 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdvc_hip.so")
 SOURCES = ["fd_kernels.hip", "fd_api.hip", "of_kernels.hip", "of_api.hip", "yuv_kernels.hip", "diag.hip",
-           "jpeg_kernels.hip", "jpeg_api.hip", "jpegd_kernels.hip", "jpegd_api.hip"]
+           "jpeg_kernels.hip", "jpeg_api.hip", "jpegd_kernels.hip", "jpegd_api.hip", "quality_kernels.hip",
+           "quality_api.hip"]
 HEADERS = ["fd_kernels.h", "dvc_device.h", "of_kernels.h", "host_common.h", "yuv_kernels.h", "yuv_px.h",
-           "jpeg_kernels.h", "jpeg_tables.h", "jpegd_kernels.h", "jpegd_core.h", "jpegd_header.h"]
+           "jpeg_kernels.h", "jpeg_tables.h", "jpegd_kernels.h", "jpegd_core.h", "jpegd_header.h", "quality_kernels.h",
+           "quality_core.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 DVC_OK = 0
@@ -53,9 +55,10 @@ EXPORTS = [
     "dvc_fd_set_state", "dvc_of_set_state", "dvc_fd_ktime_kernel", "dvc_of_ktime_kernel",
     "dvc_fd_graph_stats", "dvc_jpeg_create", "dvc_jpeg_destroy", "dvc_jpeg_header", "dvc_jpeg_bound",
     "dvc_jpeg_encode", "dvc_jpeg_sync", "dvc_jpegd_create", "dvc_jpegd_destroy", "dvc_jpegd_set_header",
-    "dvc_jpegd_decode", "dvc_jpegd_sync",
+    "dvc_jpegd_decode", "dvc_jpegd_sync", "dvc_quality_create", "dvc_quality_compare", "dvc_quality_sync",
+    "dvc_quality_destroy",
 ]
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_BATCH = 512
 
 
@@ -257,6 +260,15 @@ def lib() -> ctypes.CDLL:
     L.dvc_jpegd_decode.argtypes = [vp, u8p, ctypes.c_size_t, vp, ctypes.c_int, u8p, ctypes.c_size_t, ctypes.c_size_t, vp]
     L.dvc_jpegd_sync.argtypes = [vp]
     for name in ("dvc_jpegd_create", "dvc_jpegd_set_header", "dvc_jpegd_decode", "dvc_jpegd_sync"):
+        getattr(L, name).restype = ctypes.c_int
+    L.dvc_quality_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint32,
+                                     ctypes.POINTER(vp)]
+    L.dvc_quality_compare.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_size_t,
+                                      ctypes.c_int, vp]
+    L.dvc_quality_sync.argtypes = [vp]
+    L.dvc_quality_destroy.argtypes = [vp]
+    L.dvc_quality_destroy.restype = None
+    for name in ("dvc_quality_create", "dvc_quality_compare", "dvc_quality_sync"):
         getattr(L, name).restype = ctypes.c_int
     L.dvc_bgr_to_i420.restype = ctypes.c_int
     for name in ("dvc_of_create", "dvc_of_prime", "dvc_of_step", "dvc_of_step_batch", "dvc_of_sync",
@@ -550,6 +562,60 @@ class JpegDecoder:
     def close(self):
         if getattr(self, "_h", None):
             lib().dvc_jpegd_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# dvc_quality_frame (include/dvc.h) as a numpy record
+QUALITY_FRAME = [("sse", "<u8", (4,)), ("ssim_q32", "<i8"), ("windows", "<u4"), ("pixels", "<u4")]
+
+
+class QualityMeter:
+    """The quality meter on the GPU (dvc_quality): reference and test frames,
+    (n, H, W, 3) BGR uint8 with n <= ``max_batch`` — any strides whose pixels are
+    3 contiguous bytes and whose rows are >= 3 W bytes apart are read as they
+    are, page-locked buffers (:func:`pinned`) without a staging copy — -> one
+    ``QUALITY_FRAME`` record per pair: the exact integers DESIGN.md "Quality
+    metrics" defines; :mod:`quality` derives PSNR and SSIM from them."""
+
+    def __init__(self, width: int, height: int, device: int = 0, max_batch: int = 8):
+        self.W, self.H, self.max_batch = int(width), int(height), int(max_batch)
+        self._h = None
+        h = ctypes.c_void_p()
+        check(lib().dvc_quality_create(self.W, self.H, self.max_batch, int(device), None, 0, ctypes.byref(h)))
+        self._h = h
+
+    def _rows(self, frames):
+        """``frames`` as (array, pitch, frame stride) the C-ABI can read in place."""
+        import numpy as np
+        f = np.asarray(frames)
+        if f.dtype != np.uint8 or f.ndim != 4 or f.shape[1:] != (self.H, self.W, 3):
+            raise ValueError(f"frames {f.shape} {f.dtype} do not match (n, {self.H}, {self.W}, 3) uint8")
+        n, fs, pitch = f.shape[0], f.strides[0], f.strides[1]
+        if f.strides[2:] != (3, 1) or pitch < 3 * self.W or (n > 1 and fs < pitch * (self.H - 1) + 3 * self.W):
+            f = np.ascontiguousarray(f)
+            fs, pitch = f.strides[0], f.strides[1]
+        return f, pitch, fs
+
+    def compare(self, ref, test):
+        import numpy as np
+        a, ap, as_ = self._rows(ref)
+        b, bp, bs = self._rows(test)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError(f"{a.shape[0]} reference frames against {b.shape[0]} test frames")
+        out = np.zeros(a.shape[0], QUALITY_FRAME)
+        check(lib().dvc_quality_compare(self._h, a.ctypes.data, ap, as_, b.ctypes.data, bp, bs, a.shape[0],
+                                        out.ctypes.data))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dvc_quality_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1,0 +1,141 @@
+// quality_api.hip — C-ABI of the quality meter (include/dvc.h, dvc_quality_*):
+// what a size figure of performance_analysis.py lacks, the distortion of a
+// compressed output against its source. The arithmetic is DESIGN.md "Quality
+// metrics" (quality_core.h); the kernels are in quality_kernels.hip.
+#include "../../include/dvc.h"
+#include "host_common.h"
+#include "quality_kernels.h"
+
+using dvc_host::fail;
+
+static_assert(sizeof(dvc_quality_frame) == sizeof(dvc::QualityFrame) && sizeof(dvc_quality_frame) == 48,
+              "quality_kernels.h restates dvc_quality_frame");
+
+struct dvc_quality {
+    dvc::QualityGeom g{};
+    int device = -1, max_batch = 1;
+    uint32_t flags = 0;
+    hipStream_t stream = nullptr;   // the caller's (may be NULL = legacy default) or our own
+    bool own_stream = false;
+    uint64_t* d_part = nullptr;     // five words per tile and frame
+    // host-pointer mode: both staged batches (rows of ip bytes) and the records
+    uint8_t *d_a = nullptr, *d_b = nullptr;
+    dvc::QualityFrame* d_res = nullptr;
+    size_t ip = 0;
+};
+
+static void quality_free(dvc_quality* h)
+{
+    for (void* p : {(void*)h->d_part, (void*)h->d_a, (void*)h->d_b, (void*)h->d_res})
+        if (p) (void)hipFree(p);
+    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+}
+
+// n host frames up into rows of h->ip bytes: packed frames in one copy each (a
+// 2-D copy of pageable memory goes row by row), a packed batch in one.
+static int stage(dvc_quality* h, uint8_t* dst, const uint8_t* src, size_t pitch, size_t stride, int n)
+{
+    const size_t roww = 3 * (size_t)h->g.W, H = h->g.H;
+    const bool packed = pitch == roww && roww == h->ip;
+    if (packed && (n == 1 || stride == roww * H)) {
+        HIP_OK(hipMemcpyAsync(dst, src, (size_t)n * roww * H, hipMemcpyHostToDevice, h->stream));
+        return DVC_OK;
+    }
+    for (int t = 0; t < n; ++t) {
+        const uint8_t* s = src + (size_t)t * stride;
+        if (packed)
+            HIP_OK(hipMemcpyAsync(dst + t * roww * H, s, roww * H, hipMemcpyHostToDevice, h->stream));
+        else
+            HIP_OK(hipMemcpy2DAsync(dst + t * h->ip * H, h->ip, s, pitch, roww, H, hipMemcpyHostToDevice, h->stream));
+    }
+    return DVC_OK;
+}
+
+extern "C" {
+
+int dvc_quality_create(int width, int height, int max_batch, int device, void* hip_stream, uint32_t flags,
+                       dvc_quality** out)
+{
+    if (!out) return fail(DVC_E_INVALID, "NULL argument");
+    *out = nullptr;
+    if (width < 8 || height < 8)
+        return fail(DVC_E_UNSUPPORTED, "frame %dx%d has no 8x8 window", width, height);
+    if (width > 65535 || height > 65535) return fail(DVC_E_INVALID, "frame %dx%d invalid", width, height);
+    if (max_batch < 1 || max_batch > DVC_MAX_BATCH) return fail(DVC_E_INVALID, "max_batch %d outside 1..%d", max_batch,
+                                                                DVC_MAX_BATCH);
+    if (flags & ~(DVC_FLAG_DEVICE_PTRS | DVC_FLAG_JOIN_STREAM)) return fail(DVC_E_INVALID, "unknown flags 0x%x", flags);
+    dvc_quality* h = new dvc_quality();
+    h->g = dvc::quality_geom(width, height);
+    h->device = device;
+    h->max_batch = max_batch;
+    h->flags = flags;
+    h->ip = (3 * (size_t)width + 3) & ~(size_t)3;
+    const size_t mb = max_batch, tiles = (size_t)h->g.tiles_x * h->g.tiles_y;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) {
+        if (hip_stream || (flags & DVC_FLAG_JOIN_STREAM)) {
+            h->stream = (hipStream_t)hip_stream;
+        } else {
+            e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+            h->own_stream = e == hipSuccess;
+        }
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_part, mb * tiles * 5 * sizeof(uint64_t));
+    if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
+        e = hipMalloc((void**)&h->d_a, mb * h->ip * height);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_b, mb * h->ip * height);
+        if (e == hipSuccess) e = hipMalloc((void**)&h->d_res, mb * sizeof(dvc::QualityFrame));
+    }
+    if (e != hipSuccess) {
+        quality_free(h);
+        delete h;
+        return fail(e == hipErrorOutOfMemory ? DVC_E_NOMEM : DVC_E_HIP, "quality create: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return DVC_OK;
+}
+
+int dvc_quality_compare(dvc_quality* h, const uint8_t* ref, size_t ref_pitch, size_t ref_stride, const uint8_t* test,
+                        size_t test_pitch, size_t test_stride, int n, dvc_quality_frame* results)
+{
+    if (!h || !ref || !test || !results) return fail(DVC_E_INVALID, "NULL argument");
+    if (n < 1 || n > h->max_batch) return fail(DVC_E_INVALID, "frame count %d outside 1..%d", n, h->max_batch);
+    const size_t roww = 3 * (size_t)h->g.W, H = h->g.H;
+    if (ref_pitch < roww || test_pitch < roww) return fail(DVC_E_INVALID, "pitch invalid");
+    if (n > 1 && (ref_stride < ref_pitch * (H - 1) + roww || test_stride < test_pitch * (H - 1) + roww))
+        return fail(DVC_E_INVALID, "frame stride invalid");
+    HIP_OK(hipSetDevice(h->device));
+    auto* res = reinterpret_cast<dvc::QualityFrame*>(results);
+    if (h->flags & DVC_FLAG_DEVICE_PTRS) {
+        if ((uintptr_t)results & 7) return fail(DVC_E_INVALID, "results must be 8-byte aligned");
+        HIP_OK(dvc::quality_launch(ref, ref_pitch, ref_stride, test, test_pitch, test_stride, n, h->g, h->d_part, res,
+                                   h->stream));
+        return DVC_OK;
+    }
+    if (int rc = stage(h, h->d_a, ref, ref_pitch, ref_stride, n)) return rc;
+    if (int rc = stage(h, h->d_b, test, test_pitch, test_stride, n)) return rc;
+    HIP_OK(dvc::quality_launch(h->d_a, h->ip, h->ip * H, h->d_b, h->ip, h->ip * H, n, h->g, h->d_part, h->d_res,
+                               h->stream));
+    HIP_OK(hipMemcpyAsync(res, h->d_res, n * sizeof(dvc::QualityFrame), hipMemcpyDeviceToHost, h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return DVC_OK;
+}
+
+int dvc_quality_sync(dvc_quality* h)
+{
+    if (!h) return fail(DVC_E_INVALID, "NULL handle");
+    HIP_OK(hipSetDevice(h->device));
+    HIP_OK(hipStreamSynchronize(h->stream));
+    return DVC_OK;
+}
+
+void dvc_quality_destroy(dvc_quality* h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    quality_free(h);
+    delete h;
+}
+
+}  // extern "C"

@@ -1,0 +1,76 @@
+// quality_core.h — the quality meter's arithmetic (DESIGN.md "Quality metrics"),
+// as plain C++ that compiles for the device (quality_kernels.hip) and for the
+// host (tools/quality_host_check.cc runs the same text under the host
+// sanitizers): the luma, one pixel pair's contribution to its 4x4 cell, and the
+// value of one 8x8 SSIM window from the sums of its four cells. Every result is
+// an integer, so any summation order gives the same frame record.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#ifndef DVC_HD
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define DVC_HD __host__ __device__ __forceinline__
+#else
+#define DVC_HD inline
+#endif
+#endif
+
+namespace dvc {
+
+constexpr int kQualitySsimC1 = 416;      // (int)(.01^2 * 255^2 * 64 + .5)
+constexpr int kQualitySsimC2 = 235963;   // (int)(.03^2 * 255^2 * 64 * 63 + .5)
+
+// Luma sums of one 4x4 cell of a frame pair: s1 = sum a, s2 = sum b,
+// ss = sum (a^2 + b^2), s12 = sum a b. A window is four cells: s1, s2 <= 16320,
+// ss <= 8323200, s12 <= 4161600.
+struct QualityCell {
+    int s1, s2, ss, s12;
+};
+
+// The project's gray (gray_px in dvc_device.h): OpenCV BGR2GRAY 8U.
+DVC_HD uint32_t quality_luma(uint32_t b, uint32_t g, uint32_t r)
+{
+    return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
+}
+
+// One pixel of the reference (a) and of the test frame (b): its squared errors
+// go to sse[0..2] (B, G, R) and sse[3] (luma), its luma to the cell's sums. A
+// 32-bit sse[] holds 66051 pixels (65025 each at the most).
+DVC_HD void quality_px(uint32_t ab, uint32_t ag, uint32_t ar, uint32_t bb, uint32_t bg, uint32_t br, uint32_t (&sse)[4],
+                       QualityCell& c)
+{
+    const int db = (int)ab - (int)bb, dg = (int)ag - (int)bg, dr = (int)ar - (int)br;
+    const int ya = (int)quality_luma(ab, ag, ar), yb = (int)quality_luma(bb, bg, br);
+    sse[0] += (uint32_t)(db * db);
+    sse[1] += (uint32_t)(dg * dg);
+    sse[2] += (uint32_t)(dr * dr);
+    sse[3] += (uint32_t)((ya - yb) * (ya - yb));
+    c.s1 += ya;
+    c.s2 += yb;
+    c.ss += ya * ya + yb * yb;
+    c.s12 += ya * yb;
+}
+
+DVC_HD QualityCell quality_add(const QualityCell& p, const QualityCell& q)
+{
+    return {p.s1 + q.s1, p.s2 + q.s2, p.ss + q.ss, p.s12 + q.s12};
+}
+
+// One 8x8 window from its 64-pixel sums: the integer SSIM of x264 / ffmpeg's
+// ssim filter, A B / (C D) in IEEE f64 (two multiplies, one correctly rounded
+// divide, no contraction: the library and the host check are built with
+// -ffp-contract=off), times 2^32, rounded half to even. A, B, C, D stay below
+// 2^31 in magnitude; C, D > 0 (vars >= 0 by Cauchy-Schwarz).
+DVC_HD int64_t quality_window_q32(const QualityCell& w)
+{
+    const int s1 = w.s1, s2 = w.s2;
+    const int vars = 64 * w.ss - s1 * s1 - s2 * s2, cov = 64 * w.s12 - s1 * s2;
+    const int A = 2 * s1 * s2 + kQualitySsimC1, B = 2 * cov + kQualitySsimC2;
+    const int C = s1 * s1 + s2 * s2 + kQualitySsimC1, D = vars + kQualitySsimC2;
+    const double v = ((double)A * (double)B) / ((double)C * (double)D);
+    return (int64_t)llrint(v * 4294967296.0);
+}
+
+}  // namespace dvc

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define DVC_ABI_VERSION 9
+#define DVC_ABI_VERSION 10
 #define DVC_MAX_BATCH 512
 
 /* ---- status codes ---------------------------------------------------------- */
@@ -558,6 +558,43 @@ int dvc_jpegd_set_header(dvc_jpegd* h, const uint8_t* hdr, size_t n, size_t* hea
 int dvc_jpegd_decode(dvc_jpegd* h, const uint8_t* data, size_t data_stride, const uint32_t* sizes, int n, uint8_t* out,
                      size_t pitch, size_t frame_stride, int32_t* status);
 int dvc_jpegd_sync(dvc_jpegd* h);
+
+/* ---- quality metrics (what a size reduction costs in picture quality) ------------ */
+/* The distortion of a test frame against its reference, both packed BGR of one
+ * size: per frame the squared error of B, G, R and luma and the integer 8x8 SSIM
+ * of the luma (x264 / ffmpeg's ssim filter), as exact integers in any summation
+ * order; PSNR and SSIM follow on the host in float64. DESIGN.md "Quality
+ * metrics" is the normative text. Not a reference interface: the reference's
+ * performance_analysis.py reports sizes only. */
+typedef struct dvc_quality_frame {
+    uint64_t sse[4];   /* sum (ref - test)^2 over all W*H pixels: B, G, R, luma (the
+                          project's gray, OpenCV BGR2GRAY, of each frame) */
+    int64_t ssim_q32;  /* sum over the windows of llrint(ssim * 2^32): 8x8 windows at
+                          every (4i, 4j), i <= W/4 - 2, j <= H/4 - 2 */
+    uint32_t windows;  /* (W/4 - 1) * (H/4 - 1) */
+    uint32_t pixels;   /* W * H */
+} dvc_quality_frame;
+
+typedef struct dvc_quality dvc_quality;
+
+/* A meter for width x height frames (8..65535 each; smaller frames have no window:
+ * DVC_E_UNSUPPORTED), max_batch (1..DVC_MAX_BATCH) frame pairs per call.
+ * hip_stream / flags as dvc_jpegd_create (DVC_FLAG_DEVICE_PTRS,
+ * DVC_FLAG_JOIN_STREAM; any other flag is DVC_E_INVALID). */
+int dvc_quality_create(int width, int height, int max_batch, int device, void* hip_stream, uint32_t flags,
+                       dvc_quality** out);
+
+/* Compare n (1..max_batch) frame pairs: reference frame t at ref + t*ref_stride in
+ * rows of ref_pitch >= 3*W bytes, test frame t at test + t*test_stride in rows of
+ * test_pitch >= 3*W bytes (any pitch and alignment, read in place), its record in
+ * results[t]. Host pointers: returns after the records have landed.
+ * DVC_FLAG_DEVICE_PTRS: ref, test and results (8-byte aligned) are device
+ * pointers and the call is asynchronous on the handle's stream (the caller's
+ * when one was joined); dvc_quality_sync waits. */
+int dvc_quality_compare(dvc_quality* h, const uint8_t* ref, size_t ref_pitch, size_t ref_stride, const uint8_t* test,
+                        size_t test_pitch, size_t test_stride, int n, dvc_quality_frame* results);
+int dvc_quality_sync(dvc_quality* h);
+void dvc_quality_destroy(dvc_quality* h);
 
 /* The Q8 fixed-point Gaussian taps OpenCV's bit-exact 8U GaussianBlur uses
  * (getGaussianKernelBitExact + error-diffusion rounding to 8 fraction bits).

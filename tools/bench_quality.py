@@ -1,0 +1,145 @@
+"""Quality-meter throughput (GPU box): dvc_quality_compare on device-resident
+1080p BGR frames, the synthetic clip against its quality-75 JPEG round trip
+(the project's GPU encoder and decoder), batches of 32, device pointers on a
+joined stream, timed with device events around `steps` calls (5 runs after a
+warm-up). Prints one JSON line: Mpx/s, the bytes read per second (6 B a pixel:
+both frames once) against dvc_copy_rate on the same box in the same run, the
+one-core time of the numpy reference (tests/quality_ref.py) on the same frames,
+and — with --kernels, from a second run of this script under rocprofv3
+--kernel-trace --stats — the time of each kernel per batch. The records of the
+timed batch are checked against the reference on two frames.
+  python tools/bench_quality.py [--kernels] [--out FILE] [--width W --height H --batch B --quality Q]
+"""
+import argparse
+import csv
+import ctypes
+import glob
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+
+
+def kernel_times(a):
+    """{kernel: microseconds per launch} from a profiled child run (3 steps)."""
+    d = tempfile.mkdtemp(prefix="dvc_quality_prof_")
+    try:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "t", "--output-format", "csv", "--",
+               sys.executable, os.path.abspath(__file__), "--steps", "3", "--runs", "1", "--no-copy-rate", "--no-reference",
+               "--width", str(a.width), "--height", str(a.height), "--batch", str(a.batch), "--quality", str(a.quality)]
+        subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, timeout=300)
+        out = {}
+        for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+            for row in csv.DictReader(open(path)):
+                if "k_quality_" in row["Name"]:
+                    name = "k_quality_" + row["Name"].split("k_quality_")[1].split("(")[0].split("<")[0]
+                    out[name] = {"us_per_launch": round(float(row["AverageNs"]) / 1e3, 1), "launches": int(row["Calls"])}
+        return out
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--quality", type=int, default=75)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--no-copy-rate", action="store_true")
+    ap.add_argument("--no-reference", action="store_true")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from dvc_amd import _native as N
+    from dvc_amd.synthetic import SyntheticClip
+
+    W, H, B = a.width, a.height, a.batch
+    L = N.lib()
+    clip = SyntheticClip(W, H, seed=0)
+    ref = np.stack([clip.frame(t) for t in range(B)])
+    enc, dec = N.JpegEncoder(W, H, True, a.quality, max_batch=8), N.JpegDecoder(W, H, max_batch=8)
+    test, jpeg_bytes = [], 0
+    for f0 in range(0, B, 8):
+        samples = [enc.header + p for p in enc.encode(ref[f0:f0 + 8])]
+        jpeg_bytes += sum(len(s) for s in samples)
+        test += dec.decode(samples)
+    enc.close()
+    dec.close()
+    test = np.stack(test)
+    d_ref, d_test = torch.from_numpy(ref).cuda(), torch.from_numpy(test).cuda()
+    rec_size = np.dtype(N.QUALITY_FRAME).itemsize
+    d_res = torch.zeros(B * rec_size, dtype=torch.uint8, device="cuda")
+    s = torch.cuda.Stream()
+    h = ctypes.c_void_p()
+    N.check(L.dvc_quality_create(W, H, B, 0, ctypes.c_void_p(s.cuda_stream), N.DVC_FLAG_DEVICE_PTRS, ctypes.byref(h)))
+
+    def call():
+        N.check(L.dvc_quality_compare(h, d_ref.data_ptr(), 3 * W, 3 * W * H, d_test.data_ptr(), 3 * W, 3 * W * H, B,
+                                      d_res.data_ptr()))
+
+    with torch.cuda.stream(s):
+        for _ in range(a.warmup):
+            call()
+        s.synchronize()
+        ms = []
+        for _ in range(a.runs):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            for _ in range(a.steps):
+                call()
+            e1.record(s)
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1) / a.steps)
+    N.check(L.dvc_quality_sync(h))
+    L.dvc_quality_destroy(h)
+    rec = d_res.cpu().numpy().view(N.QUALITY_FRAME)
+    from dvc_amd import quality
+    summary = quality.summarize(rec)
+    best = float(np.median(ms))
+    px = B * W * H
+    res = {
+        "metric": "quality meter, device-resident BGR pairs -> frame records (dvc_quality_compare)",
+        "value": round(px / best / 1e3, 1), "unit": "Mpixels/s",
+        "frame_pairs_per_s": round(B / best * 1e3, 1), "ms_per_batch": round(best, 4),
+        "timing": {"ms_per_batch_per_run": [round(m, 4) for m in ms], "steps": a.steps, "warmup": a.warmup,
+                   "value_per_run": [round(px / m / 1e3, 1) for m in ms], "timed_with": "device events, joined stream"},
+        "config": {"width": W, "height": H, "batch": B, "quality": a.quality,
+                   "data": "synthetic clip seed 0 against its Motion-JPEG round trip", "io": "device"},
+        "read_GBps": round(6 * px / best / 1e6, 1),
+        "clip": {"psnr_y_dB": round(summary["psnr_y"], 3), "psnr_bgr_dB": round(summary["psnr_bgr"], 3),
+                 "ssim_y": round(summary["ssim_y"], 5), "bits_per_pixel": round(8 * jpeg_bytes / px, 3)},
+    }
+    if not a.no_copy_rate:
+        # dvc_copy_rate counts bytes read + written; the meter only reads
+        res["copy_rate_GBps"] = round(N.copy_rate(0), 1)
+        res["read_frac_of_copy_rate"] = round(res["read_GBps"] / res["copy_rate_GBps"], 4)
+    if not a.no_reference:
+        from tests import quality_ref as R
+        t0 = time.perf_counter()
+        want = R.records(ref[:2], test[:2])
+        res["numpy_reference_s_per_frame_pair"] = round((time.perf_counter() - t0) / 2, 4)
+        res["equals_reference"] = bool(np.array_equal(rec[:2], want))
+        if not res["equals_reference"]:
+            raise SystemExit("the timed batch's records differ from the reference")
+    if a.kernels:
+        res["kernels"] = kernel_times(a)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
