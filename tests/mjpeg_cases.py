@@ -65,11 +65,44 @@ ALL = {**CASES, **EXTRA}
 GRAY_CASE = "noise70x37_q90"
 
 
+def _hd(seed):
+    """1920x1080: a synthetic surveillance frame, its right third replaced by noise
+    (long segments, 0xFF bytes to stuff)."""
+    from dvc_amd.synthetic import SyntheticClip
+    f = SyntheticClip(1920, 1080, seed=seed).frame(3).copy()
+    f[:, 1280:] = _noise(640, 1080, 20 + seed)
+    return f
+
+
+# The sizes at which the encoder's loops take a later trip (tests/test_mjpeg_sizes.py asserts
+# each property from the reference's own output; tests/test_mjpeg_sizes_gpu.py runs the kernels).
+# Kept out of ALL: the parametrised tests above do not grow.
+SIZE_CASES = {
+    "tall8x2056_gray": (lambda: _smooth_noise(8, 2056, 21), 75),       # one component: 257 segments
+    "tall16x4112": (lambda: _smooth_noise(16, 4112, 22), 75),          # colour: 257 segments
+    "dense176x16_q100": (lambda: _noise(176, 16, 23), 100),            # 66 blocks a segment at Q = 1
+    "dense520x8_q100_gray": (lambda: _noise(520, 8, 24), 100),         # one component: 65 blocks
+}
+SIZE_GRAY = {"tall8x2056_gray": True, "tall16x4112": False, "dense176x16_q100": False, "dense520x8_q100_gray": True}
+# two different frames (variants 0 and 1); too large for a whole-frame reference: segment_reference
+HD_CASE = "hd1920x1080"
+HD_CASES = {HD_CASE: ((lambda: _hd(5), lambda: _hd(6)), 75)}
+_EVERY = {**ALL, **SIZE_CASES}
+
+
+def quality(name):
+    return HD_CASES[name][1] if name in HD_CASES else _EVERY[name][1]
+
+
 @functools.lru_cache(maxsize=None)
 def frame(name, variant=0):
-    """variant 1: the frame turned by 180 degrees (a second, different frame of a batch)."""
-    f = ALL[name][0]()
-    f = f[::-1, ::-1] if variant else f
+    """variant 1: the frame turned by 180 degrees (a second, different frame of a batch);
+    of HD_CASES: the second frame."""
+    if name in HD_CASES:
+        f = HD_CASES[name][0][variant]()
+    else:
+        f = _EVERY[name][0]()
+        f = f[::-1, ::-1] if variant else f
     f = np.ascontiguousarray(f)
     f.setflags(write=False)
     return f
@@ -77,5 +110,62 @@ def frame(name, variant=0):
 
 @functools.lru_cache(maxsize=None)
 def reference(name, variant=0, gray=False):
+    assert name not in HD_CASES, "too slow as a whole frame: segment_reference"
     f = frame(name, variant)
-    return mjpeg_ref.encode(f[..., 1] if gray else f, ALL[name][1])
+    return mjpeg_ref.encode(f[..., 1] if gray else f, _EVERY[name][1])
+
+
+@functools.lru_cache(maxsize=None)
+def _strip_reference(name, variant, i, gray):
+    f = frame(name, variant)
+    m = 8 if gray else 16
+    assert 0 <= i * m < f.shape[0]
+    strip = f[i * m:i * m + m]
+    return mjpeg_ref.encode(strip[..., 1] if gray else strip, quality(name))
+
+
+def segment_reference(name, variant, i, gray=False):
+    """Restart segment i of a frame (its entropy bytes, without the RST marker or EOI
+    behind them), from the reference encoder run on MCU row i alone. Segments are
+    independent: the DC predictors restart, chroma is subsampled inside the MCU, a
+    full strip needs no edge replication, and a partial last strip is replicated
+    downwards exactly as the whole frame's bottom is."""
+    s = _strip_reference(name, variant, i, gray)["stream"]
+    assert s[-2:] == b"\xff\xd9"
+    return s[:-2]
+
+
+def segment_stuffed(name, variant, i, gray=False):
+    """How many 0xFF bytes of segment i the reference stuffed."""
+    return _strip_reference(name, variant, i, gray)["stuffed"]
+
+
+def split_stream(stream):
+    """Entropy data -> ([segment bytes], [the marker byte behind each]). In entropy data
+    0xFF is followed by 0x00 or by a marker's second byte."""
+    b = np.frombuffer(stream, np.uint8)
+    segs, marks, a = [], [], 0
+    for i in np.nonzero((b[:-1] == 0xFF) & (b[1:] != 0))[0].tolist():
+        segs.append(stream[a:i])
+        marks.append(stream[i + 1])
+        a = i + 2
+    assert a == len(stream), "the stream ends with a marker"
+    return segs, marks
+
+
+@functools.lru_cache(maxsize=None)
+def block_bit_offsets(name, variant=0, gray=False, seg=0):
+    """(bit offset of every block of restart segment `seg` in scan order, the segment's bits),
+    by the reference's own block coder on the reference's levels."""
+    ref = reference(name, variant, gray)
+    info, lv = ref["info"], ref["levels"]
+    tabs = {cid: (info["huff"][(0, td)], info["huff"][(1, ta)]) for cid, td, ta in info["scan"]}
+    tabs = [tabs[c[0]] for c in info["comps"]]
+    bits, pred, off = mjpeg_ref._Bits(), [0, 0, 0], []
+    for mx in range(info["dri"]):
+        order = [(0, seg, mx)] if gray else [(0, 2 * seg + dy, 2 * mx + dx) for dy in (0, 1) for dx in (0, 1)] + \
+            [(1, seg, mx), (2, seg, mx)]
+        for c, by, bx in order:
+            off.append(bits.n)
+            pred[c] = mjpeg_ref._code_block(bits, lv[c][by, bx], pred[c], *tabs[c])
+    return off, bits.n
