@@ -9,6 +9,7 @@ fallback: if the HIP library is missing or fails to load, :func:`lib` raises.
 from __future__ import annotations
 
 import ctypes
+import glob
 import os
 import shutil
 import subprocess
@@ -16,12 +17,6 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdvc_hip.so")
-SOURCES = ["fd_kernels.hip", "fd_api.hip", "of_kernels.hip", "of_api.hip", "yuv_kernels.hip", "diag.hip",
-           "jpeg_kernels.hip", "jpeg_api.hip", "jpegd_kernels.hip", "jpegd_api.hip", "quality_kernels.hip",
-           "quality_api.hip"]
-HEADERS = ["fd_kernels.h", "dvc_device.h", "of_kernels.h", "host_common.h", "yuv_kernels.h", "yuv_px.h",
-           "jpeg_kernels.h", "jpeg_tables.h", "jpegd_kernels.h", "jpegd_core.h", "jpegd_header.h", "quality_kernels.h",
-           "quality_core.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 DVC_OK = 0
@@ -129,12 +124,17 @@ class OfParams(ctypes.Structure):
 OfStats = FdStats   # same four counters (dvc_of_stats)
 
 
+def sources() -> list:
+    """What the library is compiled from: every csrc/*.hip (tools/build_variant.sh takes the same files)."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(PKG_DIR, "..", "include", "dvc.h")]
+    srcs = sources()
+    deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(PKG_DIR, "..", "include", "dvc.h")]
     if not force and os.path.exists(LIB_PATH):
-        newest = max(os.path.getmtime(d) for d in deps if os.path.exists(d))
+        newest = max(os.path.getmtime(d) for d in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"

@@ -11,7 +11,7 @@
 
 namespace dvc {
 
-// The 4x4 DCT basis as dct_matrix(4) builds it on the host (fd_api.hip:
+// The 4x4 DCT basis as dct_matrix(4) builds it on the host (host_common.hip:
 // (float)(c * cos(pi (2n+1) k / 8))), as compile-time constants: the fused
 // front's DCT then takes its factors as literals / inline constants instead
 // of 32 kernel-argument SGPRs. launch_front checks FrontOut::M against it
@@ -34,7 +34,7 @@ inline bool dct4_is_const(const DctMat& M)
 }
 
 
-// The 8x8 DCT basis as dct_matrix(8) builds it on the host (fd_api.hip:
+// The 8x8 DCT basis as dct_matrix(8) builds it on the host (host_common.hip:
 // (float)(c * cos(pi (2n+1) k / 16))), as compile-time constants: k_of_out's and
 // k_out<8>'s DCT passes take their factors as literals instead of 128 kernel-argument
 // SGPRs (which spilled). of_launch_out / launch_out check the basis they are given bit for bit.

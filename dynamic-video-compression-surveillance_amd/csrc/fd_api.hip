@@ -3,121 +3,31 @@
 // Host side of one camera feed: owns the device state the reference keeps in
 // Python locals (prev_gray fd:75-77,133; accumulated_mask fd:81,107), the
 // contour-filter scratch, and the launch sequence of fd_kernels.hip for one
-// frame (the body of the loop at frame_differencing.py:85-138).
+// frame (the body of the loop at frame_differencing.py:85-138). What it shares
+// with the other handles — the error text, the filter and DCT tables, the
+// arena of what a handle owns, the stream fork / sync, the frame contract — is
+// host_common.h and host_frames.h; also here: the calls that belong to no
+// handle (version, last error, device count, pinned memory, contour filter).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <algorithm>
 #include <cstring>
-#include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/dvc.h"
-#include "dct_const.h"
 #include "fd_kernels.h"
 #include "klaunch.h"
 #include "host_common.h"
 #include "yuv_kernels.h"
 #include "tune.h"
 
-namespace dvc_host {
-
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-const char* last_error() { return g_err.c_str(); }
-
-// getGaussianKernelBitExact in double (OpenCV 4.11): the small binomial tables
-// for sigma <= 0 and n <= 7, else exp(-x^2 / 2 sigma^2) normalised with the
-// centre tap 1/sum. The float kernels of getGaussianKernel(CV_32F) are these
-// values cast to float.
-void gauss_f64(int n, double sigma, double* k)
-{
-    if (sigma <= 0 && n <= 7) {
-        static const double t1[] = {1.0};
-        static const double t3[] = {0.25, 0.5, 0.25};
-        static const double t5[] = {0.0625, 0.25, 0.375, 0.25, 0.0625};
-        static const double t7[] = {0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125};
-        const double* t = n == 1 ? t1 : n == 3 ? t3 : n == 5 ? t5 : t7;
-        for (int i = 0; i < n; ++i) k[i] = t[i];
-        return;
-    }
-    double sx = sigma > 0 ? sigma : std::fma((double)n, 0.15, 0.35);
-    double scale2X = -0.125 / (sx * sx);
-    int n2 = (n - 1) / 2;
-    double vals[64], sum = 0.0;
-    for (int i = 0, x = 1 - n; i < n2; ++i, x += 2) {
-        vals[i] = std::exp((double)(x * x) * scale2X);
-        sum += vals[i];
-    }
-    sum = sum * 2.0 + 1.0;
-    double mul1 = 1.0 / sum;
-    for (int i = 0; i < n2; ++i) k[i] = k[n - 1 - i] = vals[i] * mul1;
-    k[n2] = mul1;
-}
-
-void dct_matrix(int B, dvc::DctMat& M)
-{
-    // the fast block sizes take the compiled tables (dct_const.h), so the host
-    // basis and the kernels' constant basis cannot differ on a host whose libm
-    // cos rounds differently
-    if (B == 4 || B == 8) {
-        const float* t = B == 4 ? dvc::kDct4Host : dvc::kDct8Host;
-        std::memcpy(M.m, t, sizeof(float) * B * B);
-        std::memcpy(M.mt, t + B * B, sizeof(float) * B * B);
-        return;
-    }
-    const double PI = 3.14159265358979323846;
-    for (int k = 0; k < B; ++k)
-        for (int n = 0; n < B; ++n) {
-            double c = k == 0 ? std::sqrt(1.0 / B) : std::sqrt(2.0 / B);
-            M.m[k * B + n] = M.mt[n * B + k] = (float)(c * std::cos(PI * (2 * n + 1) * k / (2.0 * B)));
-        }
-}
-
-}  // namespace dvc_host
-
-namespace {
-
 using dvc_host::fail;
 using dvc_host::dct_matrix;
-
-// getGaussianKernelBitExact + getGaussianKernelFixedPoint_ED (8 fraction bits):
-// the taps OpenCV's 8U GaussianBlur uses (fd:77, fd:93).
-int gauss_taps(int n, double sigma, uint16_t* taps)
-{
-    if (n < 1 || n > 63 || (n & 1) == 0) return -1;
-    double k[64];
-    dvc_host::gauss_f64(n, sigma, k);
-    int n2 = n / 2;
-    double err = 0.0;
-    long long s = 0;
-    for (int i = 0; i < n2; ++i) {
-        double adj = k[i] * 256.0 + err;
-        double v0 = std::nearbyint(adj);
-        err = adj - v0;
-        taps[i] = taps[n - 1 - i] = (uint16_t)v0;
-        s += (long long)v0;
-    }
-    taps[n2] = (uint16_t)(256 - 2 * s);
-    return 0;
-}
-
-}  // namespace
+using dvc_host::gauss_taps;
 
 // One batch's launch sequence as a HIP graph (enqueue_batch's graph path, VERDICT
 // r5 #4): the launches of the four stages as dvc::klaunch recorded them, one
@@ -168,7 +78,7 @@ struct Slot {
     // bits), so consecutive batches' filters overlap instead of queueing on
     // one shared set; grown at the slot's graph batches (graph_ccl)
     dvc::CclBufs gc{};
-    std::vector<void*> gc_mem;
+    dvc_host::DevMem gc_mem;
     int gc_frames = 0;      // frames gc holds
 };
 
@@ -239,7 +149,8 @@ struct dvc_fd {
     unsigned long long* stats = nullptr;
     unsigned long long* err = nullptr;  // first feed frame index with an odd static block side (~0: none)
     uint8_t* h_acc = nullptr;
-    std::vector<void*> extra;      // lazily allocated device buffers
+    // every device and pinned allocation and ordering event of the handle, its slots' (but gc_mem) and stages'
+    dvc_host::DevMem mem;
     // dominant-kernel timing
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -247,6 +158,27 @@ struct dvc_fd {
     bool graph_ok = true;      // short device-frame batches take the graph path (DVC_FD_GRAPH=0 at create: never)
     bool prev_graph = false;   // the last batch ran as a graph (its stages ran on its slot's graph stream)
     uint64_t graph_batches = 0, graph_builds = 0;   // batches launched as graphs, graphs built (dvc_fd_graph_stats)
+
+    ~dvc_fd()
+    {
+        for (Slot& s : slot)
+            for (FdGraph& G : s.graphs) {
+                if (G.ge) (void)hipGraphExecDestroy(G.ge);
+                if (G.g) (void)hipGraphDestroy(G.g);
+            }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        for (hipStream_t st : {s_front, s_acc, s_out, stream})
+            if (st) (void)hipStreamDestroy(st);
+    }
+    dvc_host::FrameFmt frame() const { return {fmt, sw, sh, crows}; }
+    hipError_t sync() const { return dvc_host::sync_streams({stream, s_front, s_acc, s_out}); }
+    // The caller's stream (if any) -> every internal stream: work the caller
+    // queued before this call (e.g. the copy that produced the frames, or reads
+    // of the previous outputs) happens before the call's kernels.
+    hipError_t wait_user() const
+    {
+        return has_user ? dvc_host::fork_streams(user, ev_user, {stream, s_front, s_acc, s_out}) : hipSuccess;
+    }
 };
 
 // The stream a slot's graphs are launched on: one of the handle's four streams
@@ -255,69 +187,6 @@ struct dvc_fd {
 static hipStream_t graph_stream(dvc_fd* h, int k)
 {
     return k == 0 ? h->stream : k == 1 ? h->s_acc : k == 2 ? h->s_out : h->s_front;
-}
-
-static void free_all(dvc_fd* h)
-{
-    for (int k = 0; k < NSLOT; ++k) {
-        Slot& s = h->slot[k];
-        void* dev[] = {s.c.mbits, s.c.kbits, s.c.kocc, s.dblk, s.rblk, s.sbits, s.docc, s.dbits, s.rbits, s.zbits,
-                       s.fin, s.fsrc};
-        for (void* p : dev)
-            if (p) (void)hipFree(p);
-        if (k == 0) {   // the contour filter's working arrays: one set, shared by the slots
-            void* shared[] = {s.c.fbits, s.c.rs, s.c.re, s.c.nfg, s.c.fpar, s.c.gpar, s.c.area2, s.c.gE, s.c.rowb};
-            for (void* p : shared)
-                if (p) (void)hipFree(p);
-        }
-        for (hipEvent_t e : {s.ev_front, s.ev_ccl, s.ev_acc, s.ev_out})
-            if (e) (void)hipEventDestroy(e);
-        for (FdGraph& G : s.graphs) {
-            if (G.ge) (void)hipGraphExecDestroy(G.ge);
-            if (G.g) (void)hipGraphDestroy(G.g);
-        }
-        s.graphs.clear();
-        for (void* p : s.gc_mem) (void)hipFree(p);
-        s.gc_mem.clear();
-        s.gc_frames = 0;
-    }
-    for (Stage& s : h->stage) {
-        for (void* p : {(void*)s.d_in, (void*)s.d_ov, (void*)s.d_cp})
-            if (p) (void)hipFree(p);
-        for (void* p : {(void*)s.h_in, (void*)s.h_ov, (void*)s.h_cp})
-            if (p) (void)hipHostFree(p);
-        for (hipEvent_t e : {s.ev_h2d, s.ev_d2h, s.ev_free})
-            if (e) (void)hipEventDestroy(e);
-    }
-    void* dev[] = {h->gray[0], h->gray[1], h->acc, h->dbg_dil, h->tmp32, h->gtmp, h->stats, h->err, h->Mtab,
-                   (void*)h->rt.xo, (void*)h->rt.yo};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
-    for (void* p : h->extra) (void)hipFree(p);
-    if (h->h_acc) (void)hipHostFree(h->h_acc);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {h->ev_user, h->ev_join_out, h->ev_join_acc})
-        if (e) (void)hipEventDestroy(e);
-    for (hipStream_t st : {h->s_front, h->s_acc, h->s_out, h->stream})
-        if (st) (void)hipStreamDestroy(st);
-}
-
-template <typename T>
-static hipError_t dalloc(T** p, size_t bytes)
-{
-    return hipMalloc(reinterpret_cast<void**>(p), bytes ? bytes : 16);
-}
-
-// The caller's stream (if any) -> every internal stream: work the caller queued
-// before this call (e.g. the copy that produced the frames, or reads of the
-// previous outputs) happens before the call's kernels.
-static hipError_t wait_user(dvc_fd* h)
-{
-    if (!h->has_user) return hipSuccess;
-    hipError_t e = hipEventRecord(h->ev_user, h->user);
-    for (hipStream_t st : {h->stream, h->s_front, h->s_acc, h->s_out})
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, h->ev_user, 0);
-    return e;
 }
 
 // Internal streams -> the caller's stream: work the caller queues after this
@@ -329,14 +198,6 @@ static hipError_t join_user(dvc_fd* h)
     if (e == hipSuccess) e = hipEventRecord(h->ev_join_acc, h->s_acc);
     if (e == hipSuccess) e = hipStreamWaitEvent(h->user, h->ev_join_out, 0);
     if (e == hipSuccess) e = hipStreamWaitEvent(h->user, h->ev_join_acc, 0);
-    return e;
-}
-
-static hipError_t sync_all(dvc_fd* h)
-{
-    hipError_t e = hipStreamSynchronize(h->stream);
-    for (hipStream_t st : {h->s_front, h->s_acc, h->s_out})
-        if (e == hipSuccess && st) e = hipStreamSynchronize(st);
     return e;
 }
 
@@ -353,24 +214,16 @@ static int check_stop(dvc_fd* h)
                                "implemented, fd:122)", e + 1);
 }
 
-// Can the kernels read these frames in place? (dword rows reaching 3 * gs
-// bytes; W % 4 == 0 so the last row of a frame span ends at its last quad and a
-// buffer sized to the span is never read past its end)
-static bool direct_frames(const dvc_fd* h, const uint8_t* p, size_t pitch, size_t fstride, int n)
+// How the kernels can read these device frames in place (host_frames.h
+// readable_in_place; never across a resize): 1 as BGR rows reaching 3 * gs
+// bytes, 2 as 4:2:0 surfaces (no staged BGR copy, fd_kernels.h SrcFmt;
+// DVC_FD_YUV_DIRECT=0 forces the staged conversion, A/B), 0 not at all.
+static int in_place(const dvc_fd* h, const uint8_t* p, size_t pitch, size_t fstride, int n)
 {
-    return h->fmt == DVC_FMT_BGR && !h->resize && h->p.width % 4 == 0 && pitch % 4 == 0 && pitch >= (size_t)h->ip &&
-           ((uintptr_t)p & 3) == 0 && (n <= 1 || fstride % 4 == 0);
-}
-
-// Can k_front / k_out / k_out_gen read these 4:2:0 surfaces in place (no
-// staged BGR copy, fd_kernels.h SrcFmt)? Dword luma rows (pitch % 4 == 0, so
-// rows reach gs bytes), aligned base and stride, no resize in between.
-// DVC_FD_YUV_DIRECT=0 forces the staged conversion (A/B).
-static bool direct_yuv(const dvc_fd* h, const uint8_t* p, size_t pitch, size_t fstride, int n)
-{
-    static const int on = [] { const char* e = dvc::tune_env("DVC_FD_YUV_DIRECT"); return e ? atoi(e) : 1; }();
-    return on && h->fmt != DVC_FMT_BGR && !h->resize && h->p.width % 4 == 0 && pitch % 4 == 0 &&
-           ((uintptr_t)p & 3) == 0 && (n <= 1 || fstride % 4 == 0);
+    static const int yuv_on = [] { const char* e = dvc::tune_env("DVC_FD_YUV_DIRECT"); return e ? atoi(e) : 1; }();
+    const bool bgr = h->fmt == DVC_FMT_BGR;
+    if (h->resize || !(bgr || yuv_on)) return 0;
+    return dvc_host::readable_in_place(h->p.width, p, pitch, bgr ? (size_t)h->ip : 0, fstride, n) ? (bgr ? 1 : 2) : 0;
 }
 
 static bool host_pinned(const void* p)
@@ -387,39 +240,11 @@ static hipError_t alloc_fin(dvc_fd* h)
 {
     hipError_t e = hipSuccess;
     for (Slot& s : h->slot) {
-        if (!s.fin && e == hipSuccess) e = dalloc(&s.fin, (size_t)h->ip * h->g.H * h->max_batch);
+        if (!s.fin && e == hipSuccess) e = h->mem.alloc(&s.fin, (size_t)h->ip * h->g.H * h->max_batch);
         if (!s.fsrc && h->fmt != DVC_FMT_BGR && h->resize && e == hipSuccess)
-            e = dalloc(&s.fsrc, (size_t)h->sip * h->sh * h->max_batch);
+            e = h->mem.alloc(&s.fsrc, (size_t)h->sip * h->sh * h->max_batch);
     }
     return e;
-}
-
-// Bytes a frame handed to prime/step spans (rows of `pitch`): BGR rows, or a
-// YUV 4:2:0 frame's luma + chroma planes (include/dvc.h frame layout).
-static size_t frame_span(const dvc_fd* h, size_t pitch, int crows)
-{
-    if (h->fmt == DVC_FMT_BGR) return pitch * (h->sh - 1) + 3 * (size_t)h->sw;
-    return dvc::yuv_frame_bytes(pitch, crows);
-}
-
-// Copy host frame `src` into pinned staging `dst` in the compact layout the
-// staged device copy is read with (BGR rows of sip; YUV: luma rows of sw and
-// the chroma plane(s) right after them).
-static void pack_host_frame(const dvc_fd* h, const uint8_t* src, size_t pitch, uint8_t* dst)
-{
-    const size_t sw = h->sw, sh = h->sh;
-    if (h->fmt == DVC_FMT_BGR) {
-        for (size_t y = 0; y < sh; ++y) std::memcpy(dst + y * h->sip, src + y * pitch, 3 * sw);
-        return;
-    }
-    const dvc::YuvLayout L = dvc::yuv_layout(src, pitch, h->fmt, h->crows, 0);
-    const dvc::YuvLayout C = dvc::yuv_layout(dst, sw, h->fmt, (int)sh, 0);
-    for (size_t y = 0; y < sh; ++y) std::memcpy(dst + y * sw, src + y * pitch, sw);
-    const size_t cb = h->fmt == DVC_FMT_NV12 ? sw : sw / 2;   // chroma bytes per row and plane
-    for (size_t y = 0; y < sh / 2; ++y) {
-        std::memcpy(dst + C.uoff + y * C.cpitch, src + L.uoff + y * L.cpitch, cb);
-        if (h->fmt == DVC_FMT_I420) std::memcpy(dst + C.voff + y * C.cpitch, src + L.voff + y * L.cpitch, cb);
-    }
 }
 
 extern "C" {
@@ -542,10 +367,8 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
     h->kprime.n = p.prime_ksize;
     if (h->fast) dct_matrix(p.block, h->M);
     auto bad = [&](hipError_t e, const char* what) {
-        int rc = fail(e == hipErrorOutOfMemory ? DVC_E_NOMEM : DVC_E_HIP, "%s: %s", what, hipGetErrorString(e));
-        free_all(h);
         delete h;
-        return rc;
+        return dvc_host::create_failed(e, what);
     };
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return bad(e, "hipSetDevice");
@@ -569,7 +392,7 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
     auto mk = [](hipStream_t* st, int pr) { return hipStreamCreateWithPriority(st, hipStreamNonBlocking, pr); };
     if ((e = mk(&h->stream, level(prio[1]))) != hipSuccess) return bad(e, "hipStreamCreate");
     for (hipEvent_t* ev : {&h->ev_user, &h->ev_join_out, &h->ev_join_acc})
-        if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+        if ((e = h->mem.event(ev)) != hipSuccess) return bad(e, "hipEventCreate");
     for (auto sp : {std::make_pair(&h->s_front, level(prio[0])), std::make_pair(&h->s_acc, level(prio[2])),
                     std::make_pair(&h->s_out, level(prio[3]))})
         if ((e = mk(sp.first, sp.second)) != hipSuccess) return bad(e, "hipStreamCreate");
@@ -608,8 +431,9 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
         Slot& s = h->slot[k];
         size_t sz[dvc::CclBufs::NARR];
         dvc::CclBufs::sizes(h->g, mb, sz);
-        void** ptrs[dvc::CclBufs::NARR];
+        void **ptrs[dvc::CclBufs::NARR], **ptrs0[dvc::CclBufs::NARR];
         s.c.ptrs(ptrs);
+        h->slot[0].c.ptrs(ptrs0);
         // Only the motion bits (written by the front of a later batch while this
         // one's contour filter runs) and the kept bits (read by the accumulate
         // stage after it) belong to a slot; the filter's run index, parents,
@@ -617,37 +441,25 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
         // inside the contour-filter stage, whose batches run one after another
         // on the handle's stream: one set serves all slots.
         for (int i = 0; i < dvc::CclBufs::NARR; ++i) {
-            if (dvc::CclBufs::working_set(i) && k > 0) continue;   // slot 0's, set below
-            if ((e = dalloc(ptrs[i], sz[i])) != hipSuccess) return bad(e, "hipMalloc");
-        }
-        if (k > 0) {
-            const dvc::CclBufs& c0 = h->slot[0].c;
-            s.c.rowb = c0.rowb;
-            s.c.fbits = c0.fbits;
-            s.c.rs = c0.rs;
-            s.c.re = c0.re;
-            s.c.nfg = c0.nfg;
-            s.c.fpar = c0.fpar;
-            s.c.gpar = c0.gpar;
-            s.c.gE = c0.gE;
-            s.c.area2 = c0.area2;
+            if (dvc::CclBufs::working_set(i) && k > 0) *ptrs[i] = *ptrs0[i];   // slot 0's
+            else if ((e = h->mem.alloc(ptrs[i], sz[i])) != hipSuccess) return bad(e, "hipMalloc");
         }
         // rows of the kept mask with bits (k_paint -> dilate); KEEP_PLANES reads
         // the kept mask back, so every row is written then
-        if ((e = dalloc(&s.c.kocc, H * (size_t)mb)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&s.c.kocc, H * (size_t)mb)) != hipSuccess) return bad(e, "hipMalloc");
         s.c.kfull = (p.flags & DVC_FLAG_KEEP_PLANES) ? 1 : 0;
         if (h->fast) {   // block fields: u16 (B = 4) / u64 (B = 8) per block
             const size_t fb = p.block == 4 ? 2 : 8;
-            if ((e = dalloc(&s.docc, (size_t)h->NBY * mb)) != hipSuccess) return bad(e, "hipMalloc");
-            if ((e = dalloc(&s.dblk, fb * nfield * mb)) != hipSuccess) return bad(e, "hipMalloc");
-            if ((e = dalloc(&s.rblk, fb * nfield * mb)) != hipSuccess) return bad(e, "hipMalloc");
-            if ((e = dalloc(&s.sbits, 8 * h->sstride * (size_t)mb)) != hipSuccess) return bad(e, "hipMalloc");
+            if ((e = h->mem.alloc(&s.docc, (size_t)h->NBY * mb)) != hipSuccess) return bad(e, "hipMalloc");
+            if ((e = h->mem.alloc(&s.dblk, fb * nfield * mb)) != hipSuccess) return bad(e, "hipMalloc");
+            if ((e = h->mem.alloc(&s.rblk, fb * nfield * mb)) != hipSuccess) return bad(e, "hipMalloc");
+            if ((e = h->mem.alloc(&s.sbits, 8 * h->sstride * (size_t)mb)) != hipSuccess) return bad(e, "hipMalloc");
         } else {
             for (uint64_t** q : {&s.dbits, &s.rbits, &s.zbits})
-                if ((e = dalloc(q, 8 * H * WW * (size_t)mb)) != hipSuccess) return bad(e, "hipMalloc");
+                if ((e = h->mem.alloc(q, 8 * H * WW * (size_t)mb)) != hipSuccess) return bad(e, "hipMalloc");
         }
         for (hipEvent_t* ev : {&s.ev_front, &s.ev_ccl, &s.ev_acc, &s.ev_out})
-            if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+            if ((e = h->mem.event(ev)) != hipSuccess) return bad(e, "hipEventCreate");
     }
     // staged input frames: always needed to resize or when rows are not whole quads
     if (h->resize || p.width % 4 || h->fmt != DVC_FMT_BGR) {
@@ -659,23 +471,17 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
         {(void**)&h->stats, 8 * 4 * 64}, {(void**)&h->err, 8},
     };
     for (auto& a : allocs)
-        if ((e = dalloc(a.ptr, a.bytes)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(a.ptr, a.bytes)) != hipSuccess) return bad(e, "hipMalloc");
     for (Slot& s : h->slot) s.c.stats = h->stats;
     {   // DCT bases of length B, W % B, H % B (the generic back end / partial edge blocks)
         const int B = p.block, bw = p.width % B, bh = p.height % B;
         std::vector<float> tab((size_t)B * B + bw * bw + bh * bh);
-        auto basis = [](int n, float* m) {
-            const double PI = 3.14159265358979323846;
-            for (int k = 0; k < n; ++k)
-                for (int j = 0; j < n; ++j) {
-                    const double c = k == 0 ? std::sqrt(1.0 / n) : std::sqrt(2.0 / n);
-                    m[k * n + j] = (float)(c * std::cos(PI * (2 * j + 1) * k / (2.0 * n)));
-                }
-        };
+        // (the computed form also for B = 4, 8: not the tables of dct_const.h)
+        const auto basis = dvc_host::dct_basis;
         basis(B, tab.data());
         if (bw) basis(bw, tab.data() + B * B);
         if (bh) basis(bh, tab.data() + B * B + bw * bw);
-        if ((e = dalloc(&h->Mtab, 4 * tab.size())) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&h->Mtab, 4 * tab.size())) != hipSuccess) return bad(e, "hipMalloc");
         if ((e = hipMemcpy(h->Mtab, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice)) != hipSuccess)
             return bad(e, "hipMemcpy");
     }
@@ -687,29 +493,29 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
         h->rt.dw = p.width;
         h->rt.dh = p.height;
         int *dx = nullptr, *dy = nullptr;
-        if ((e = dalloc(&dx, 4 * tx.size())) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&dx, 4 * tx.size())) != hipSuccess) return bad(e, "hipMalloc");
         h->rt.xo = dx;
-        if ((e = dalloc(&dy, 4 * ty.size())) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&dy, 4 * ty.size())) != hipSuccess) return bad(e, "hipMalloc");
         h->rt.yo = dy;
         if ((e = hipMemcpy(dx, tx.data(), 4 * tx.size(), hipMemcpyHostToDevice)) != hipSuccess) return bad(e, "hipMemcpy");
         if ((e = hipMemcpy(dy, ty.data(), 4 * ty.size(), hipMemcpyHostToDevice)) != hipSuccess) return bad(e, "hipMemcpy");
     }
     if (p.flags & DVC_FLAG_KEEP_PLANES) {
-        if ((e = dalloc(&h->dbg_dil, 8 * H * WW)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&h->dbg_dil, 8 * H * WW)) != hipSuccess) return bad(e, "hipMalloc");
     }
     if (!(p.flags & DVC_FLAG_DEVICE_PTRS)) {
         const size_t Fi = (size_t)h->sip * h->sh * mb, Fo = 3 * N * (size_t)mb;
         for (Stage& st : h->stage) {
-            if ((e = dalloc(&st.d_in, Fi)) != hipSuccess) return bad(e, "hipMalloc");
-            if ((e = dalloc(&st.d_ov, Fo)) != hipSuccess) return bad(e, "hipMalloc");
-            if ((e = dalloc(&st.d_cp, Fo)) != hipSuccess) return bad(e, "hipMalloc");
-            if ((e = hipHostMalloc((void**)&st.h_in, Fi)) != hipSuccess) return bad(e, "hipHostMalloc");
-            if ((e = hipHostMalloc((void**)&st.h_ov, Fo)) != hipSuccess) return bad(e, "hipHostMalloc");
-            if ((e = hipHostMalloc((void**)&st.h_cp, Fo)) != hipSuccess) return bad(e, "hipHostMalloc");
+            if ((e = h->mem.alloc(&st.d_in, Fi)) != hipSuccess) return bad(e, "hipMalloc");
+            if ((e = h->mem.alloc(&st.d_ov, Fo)) != hipSuccess) return bad(e, "hipMalloc");
+            if ((e = h->mem.alloc(&st.d_cp, Fo)) != hipSuccess) return bad(e, "hipMalloc");
+            if ((e = h->mem.alloc_pinned(&st.h_in, Fi)) != hipSuccess) return bad(e, "hipHostMalloc");
+            if ((e = h->mem.alloc_pinned(&st.h_ov, Fo)) != hipSuccess) return bad(e, "hipHostMalloc");
+            if ((e = h->mem.alloc_pinned(&st.h_cp, Fo)) != hipSuccess) return bad(e, "hipHostMalloc");
             for (hipEvent_t* ev : {&st.ev_h2d, &st.ev_d2h, &st.ev_free})
-                if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+                if ((e = h->mem.event(ev)) != hipSuccess) return bad(e, "hipEventCreate");
         }
-        if ((e = hipHostMalloc((void**)&h->h_acc, N)) != hipSuccess) return bad(e, "hipHostMalloc");
+        if ((e = h->mem.alloc_pinned(&h->h_acc, N)) != hipSuccess) return bad(e, "hipHostMalloc");
     }
     if ((e = hipMemsetAsync(h->stats, 0, 8 * 4 * 64, h->stream)) != hipSuccess) return bad(e, "hipMemset");
     if ((e = hipMemsetAsync(h->err, 0xff, 8, h->stream)) != hipSuccess) return bad(e, "hipMemset");
@@ -738,13 +544,14 @@ static int stage_input(dvc_fd* h, Slot& S, const uint8_t* src, size_t pitch, siz
                        const uint8_t** d, int* dp, size_t* dfs, int crows, dvc::SrcFmt* sf)
 {
     if (sf) *sf = dvc::SrcFmt{DVC_FMT_BGR, 0, 0, 0};
-    if (direct_frames(h, src, pitch, fstride, n)) {
+    const int direct = in_place(h, src, pitch, fstride, n);
+    if (direct == 1) {
         *d = src;
         *dp = (int)pitch;
         *dfs = fstride;
         return DVC_OK;
     }
-    if (sf && direct_yuv(h, src, pitch, fstride, n)) {
+    if (sf && direct == 2) {
         const dvc::YuvLayout L = dvc::yuv_layout(src, pitch, h->fmt, crows, fstride);
         *sf = dvc::SrcFmt{h->fmt, L.uoff, L.voff, L.cpitch};
         *d = src;
@@ -779,22 +586,34 @@ static int stage_input(dvc_fd* h, Slot& S, const uint8_t* src, size_t pitch, siz
     return DVC_OK;
 }
 
+// The tail of dvc_fd_prime / dvc_fd_set_state, on s_front behind the new state:
+// a new run starts, its counters and the odd-DCT stop reset.
+static int start_run(dvc_fd* h)
+{
+    HIP_OK(hipMemsetAsync(h->stats, 0, 8 * 4 * 64, h->s_front));
+    HIP_OK(hipMemsetAsync(h->err, 0xff, 8, h->s_front));
+    HIP_OK(hipStreamSynchronize(h->s_front));
+    h->frames = h->seq = h->err_frame = 0;
+    h->last_n = 0;
+    h->primed = true;
+    h->failed = h->prev_graph = false;
+    return DVC_OK;
+}
+
 extern "C" {
 
 int dvc_fd_prime(dvc_fd* h, const uint8_t* bgr, size_t pitch)
 {
     if (!h || !bgr) return fail(DVC_E_INVALID, "NULL argument");
-    if (pitch < (h->fmt == DVC_FMT_BGR ? 3 * (size_t)h->sw : (size_t)h->sw) ||
-        (h->fmt == DVC_FMT_I420 && (pitch & 1)))
-        return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
+    if (!dvc_host::pitch_ok(h->frame(), pitch)) return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
     HIP_OK(hipSetDevice(h->device));
     const size_t W = h->p.width, H = h->p.height;
     if (!h->tmp32) {
-        HIP_OK(dalloc(&h->tmp32, 4 * W * H));
-        HIP_OK(dalloc(&h->gtmp, (size_t)h->gs * H));
+        HIP_OK(h->mem.alloc(&h->tmp32, 4 * W * H));
+        HIP_OK(h->mem.alloc(&h->gtmp, (size_t)h->gs * H));
     }
-    HIP_OK(sync_all(h));  // no batch of a previous run may still be in flight
-    HIP_OK(wait_user(h));
+    HIP_OK(h->sync());  // no batch of a previous run may still be in flight
+    HIP_OK(h->wait_user());
     for (Slot& s : h->slot) s.recorded = false;
     for (Stage& s : h->stage) s.busy = false;
     const uint8_t* src = bgr;
@@ -802,7 +621,7 @@ int dvc_fd_prime(dvc_fd* h, const uint8_t* bgr, size_t pitch)
     int crows = h->crows;
     if (!(h->p.flags & DVC_FLAG_DEVICE_PTRS)) {
         Stage& st = h->stage[0];
-        pack_host_frame(h, bgr, pitch, st.h_in);
+        dvc_host::pack_host_frame(h->frame(), bgr, pitch, st.h_in, h->sip);
         HIP_OK(hipMemcpyAsync(st.d_in, st.h_in, (size_t)h->sip * h->sh, hipMemcpyHostToDevice, h->s_front));
         src = st.d_in;
         sp = h->fmt == DVC_FMT_BGR ? h->sip : h->sw;
@@ -816,17 +635,7 @@ int dvc_fd_prime(dvc_fd* h, const uint8_t* bgr, size_t pitch)
     HIP_OK(dvc::launch_prime(d, dp, h->gtmp, h->tmp32, h->gray[h->gcur], h->p.width, h->p.height, h->gs, h->kprime,
                              h->s_front));
     HIP_OK(hipMemsetAsync(h->acc, 0, (size_t)h->AP * h->NBY * h->B, h->s_front));
-    HIP_OK(hipMemsetAsync(h->stats, 0, 8 * 4 * 64, h->s_front));
-    HIP_OK(hipMemsetAsync(h->err, 0xff, 8, h->s_front));
-    HIP_OK(hipStreamSynchronize(h->s_front));
-    h->frames = 0;
-    h->seq = 0;
-    h->last_n = 0;
-    h->primed = true;
-    h->failed = false;
-    h->err_frame = 0;
-    h->prev_graph = false;
-    return DVC_OK;
+    return start_run(h);
 }
 
 // Resume a feed (checkpoint / resume): the state the reference
@@ -839,24 +648,14 @@ int dvc_fd_set_state(dvc_fd* h, const uint8_t* prev_gray, const uint8_t* acc)
     if (!h || !prev_gray || !acc) return fail(DVC_E_INVALID, "NULL argument");
     HIP_OK(hipSetDevice(h->device));
     const size_t W = h->p.width, H = h->p.height;
-    HIP_OK(sync_all(h));  // no batch of a previous run may still be in flight
-    HIP_OK(wait_user(h));
+    HIP_OK(h->sync());  // no batch of a previous run may still be in flight
+    HIP_OK(h->wait_user());
     for (Slot& s : h->slot) s.recorded = false;
     for (Stage& s : h->stage) s.busy = false;
     HIP_OK(hipMemcpy2DAsync(h->gray[h->gcur], h->gs, prev_gray, W, W, H, hipMemcpyHostToDevice, h->s_front));
     // the acc rows have pitch AP; the padding of partial blocks stays 0 (create)
     HIP_OK(hipMemcpy2DAsync(h->acc, h->AP, acc, W, W, H, hipMemcpyHostToDevice, h->s_front));
-    HIP_OK(hipMemsetAsync(h->stats, 0, 8 * 4 * 64, h->s_front));
-    HIP_OK(hipMemsetAsync(h->err, 0xff, 8, h->s_front));
-    HIP_OK(hipStreamSynchronize(h->s_front));
-    h->frames = 0;
-    h->seq = 0;
-    h->last_n = 0;
-    h->primed = true;
-    h->failed = false;
-    h->err_frame = 0;
-    h->prev_graph = false;
-    return DVC_OK;
+    return start_run(h);
 }
 
 }  // extern "C"
@@ -887,10 +686,9 @@ static int graph_ccl(dvc_fd* h, Slot& S, int n)
     int cap = 1;
     while (cap < n) cap *= 2;
     cap = std::min(cap, std::min(h->max_batch, GRAPH_OWN_CCL_FRAMES));
-    if (!S.gc_mem.empty()) {
+    if (!S.gc_mem.dev.empty()) {
         if (S.recorded) HIP_OK(hipEventSynchronize(S.ev_out));   // the slot's last batch is done with the set
-        for (void* q : S.gc_mem) (void)hipFree(q);
-        S.gc_mem.clear();
+        S.gc_mem.free_all();
         S.gc_frames = 0;
     }
     size_t sz[dvc::CclBufs::NARR];
@@ -900,16 +698,11 @@ static int graph_ccl(dvc_fd* h, Slot& S, int n)
     S.gc.ptrs(ptrs);
     for (int i = 0; i < dvc::CclBufs::NARR; ++i) {
         if (!dvc::CclBufs::working_set(i)) continue;
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, sz[i] ? sz[i] : 16);
+        const hipError_t e = S.gc_mem.alloc(ptrs[i], sz[i]);
         if (e != hipSuccess) {
-            for (void* q : S.gc_mem) (void)hipFree(q);
-            S.gc_mem.clear();
-            return fail(e == hipErrorOutOfMemory ? DVC_E_NOMEM : DVC_E_HIP, "graph contour-filter set: %s",
-                        hipGetErrorString(e));
+            S.gc_mem.free_all();
+            return dvc_host::create_failed(e, "graph contour-filter set");
         }
-        S.gc_mem.push_back(p);
-        *ptrs[i] = p;
     }
     // every frame slice's OUTSIDE gap node is its own root before any k_band (as at create)
     HIP_OK(hipMemsetAsync(S.gc.gpar, 0, sz[6], graph_stream(h, (int)(&S - h->slot))));
@@ -1104,7 +897,7 @@ static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fst
     // run ~3 % faster (experiments/README.md round 6)
     const bool graph = h->graph_ok && (h->p.flags & DVC_FLAG_DEVICE_PTRS) && !timed && !skip &&
                        (n <= GRAPH_OWN_CCL_FRAMES || overlapping.empty()) &&
-                       (direct_frames(h, src, pitch, fstride, n) || direct_yuv(h, src, pitch, fstride, n));
+                       in_place(h, src, pitch, fstride, n) != 0;
     if (!graph && h->prev_graph) {
         // the previous batch ran on its slot's graph stream: the stage streams
         // take its recurrences from its events
@@ -1316,13 +1109,13 @@ static int run_frames(dvc_fd* h, const uint8_t* bgr, size_t pitch, size_t fstrid
     if (n < 0) return fail(DVC_E_INVALID, "negative frame count");
     const size_t W = h->p.width, H = h->p.height, N = W * H, srow = 3 * (size_t)h->sw;
     const bool yuv = h->fmt != DVC_FMT_BGR;
-    if (pitch < (yuv ? (size_t)h->sw : srow) || (h->fmt == DVC_FMT_I420 && (pitch & 1)))
-        return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
-    if (n > 1 && fstride < frame_span(h, pitch, h->crows)) return fail(DVC_E_INVALID, "frame stride %zu invalid", fstride);
+    if (!dvc_host::pitch_ok(h->frame(), pitch)) return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
+    if (n > 1 && fstride < dvc_host::frame_span(h->frame(), pitch))
+        return fail(DVC_E_INVALID, "frame stride %zu invalid", fstride);
     if (n > 1 && (overlay || compressed) && ostride < h->ofb)
         return fail(DVC_E_INVALID, "output frame stride %zu invalid", ostride);
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(wait_user(h));
+    HIP_OK(h->wait_user());
     const bool devp = h->p.flags & DVC_FLAG_DEVICE_PTRS;
     if (devp) {
         for (int f0 = 0; f0 < n; f0 += h->max_batch) {
@@ -1369,7 +1162,8 @@ static int run_frames(dvc_fd* h, const uint8_t* bgr, size_t pitch, size_t fstrid
                                         hipMemcpyHostToDevice, h->s_front));
         } else {
             HIP_OK(hipEventSynchronize(st.ev_h2d));   // h_in's previous upload is done
-            for (int t = 0; t < m; ++t) pack_host_frame(h, in + (size_t)t * fstride, pitch, st.h_in + t * sfs);
+            for (int t = 0; t < m; ++t)
+                dvc_host::pack_host_frame(h->frame(), in + (size_t)t * fstride, pitch, st.h_in + t * sfs, h->sip);
             HIP_OK(hipMemcpyAsync(st.d_in, st.h_in, (size_t)m * sfs, hipMemcpyHostToDevice, h->s_front));
             HIP_OK(hipEventRecord(st.ev_h2d, h->s_front));
         }
@@ -1400,7 +1194,7 @@ static int run_frames(dvc_fd* h, const uint8_t* bgr, size_t pitch, size_t fstrid
         HIP_OK(hipStreamSynchronize(h->s_acc));
         std::memcpy(acc_out, h->h_acc, N);
     }
-    HIP_OK(sync_all(h));
+    HIP_OK(h->sync());
     HIP_OK(join_user(h));
     return check_stop(h);
 }
@@ -1423,7 +1217,7 @@ int dvc_fd_sync(dvc_fd* h)
 {
     if (!h) return fail(DVC_E_INVALID, "NULL handle");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(sync_all(h));
+    HIP_OK(h->sync());
     return check_stop(h);
 }
 
@@ -1431,11 +1225,10 @@ int dvc_fd_get_stats(dvc_fd* h, dvc_fd_stats* out)
 {
     if (!h || !out) return fail(DVC_E_INVALID, "NULL argument");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(sync_all(h));
+    HIP_OK(h->sync());
     (void)check_stop(h);
-    unsigned long long slots[64 * 4], s[4] = {0, 0, 0, 0};
-    HIP_OK(hipMemcpy(slots, h->stats, sizeof(slots), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 64 * 4; ++i) s[i % 4] += slots[i];
+    unsigned long long s[4];
+    HIP_OK(dvc_host::fold_stats(h->stats, s));
     out->frames = h->failed ? std::min<uint64_t>(h->frames, h->err_frame) : h->frames;
     out->motion_px = s[1];
     out->components = s[2];
@@ -1450,7 +1243,7 @@ int dvc_fd_read_plane(dvc_fd* h, int plane, uint8_t* dst)
     if (!h->frames && plane != DVC_PLANE_GRAY && plane != DVC_PLANE_ACC)
         return fail(DVC_E_STATE, "no frame stepped yet");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(sync_all(h));
+    HIP_OK(h->sync());
     const size_t W = h->p.width, H = h->p.height, WW = h->g.WW;
     if (plane == DVC_PLANE_GRAY) {
         HIP_OK(hipMemcpy2D(dst, W, h->gray[h->gcur], h->gs, W, H, hipMemcpyDeviceToHost));
@@ -1468,10 +1261,7 @@ int dvc_fd_read_plane(dvc_fd* h, int plane, uint8_t* dst)
     if (plane != DVC_PLANE_MOTION && plane != DVC_PLANE_FILTERED && plane != DVC_PLANE_DILATED)
         return fail(DVC_E_INVALID, "unknown plane %d", plane);
     if (!src) return fail(DVC_E_STATE, "plane %d needs DVC_FLAG_KEEP_PLANES", plane);
-    std::vector<uint64_t> bits(H * WW);
-    HIP_OK(hipMemcpy(bits.data(), src, 8 * H * WW, hipMemcpyDeviceToHost));
-    for (size_t y = 0; y < H; ++y)
-        for (size_t x = 0; x < W; ++x) dst[y * W + x] = ((bits[y * WW + x / 64] >> (x % 64)) & 1) ? 255 : 0;
+    HIP_OK(dvc_host::read_bit_plane(src, W, H, WW, dst));
     return DVC_OK;
 }
 
@@ -1479,13 +1269,10 @@ int dvc_fd_ktime(dvc_fd* h, double* total_ms, uint64_t* launches, int reset)
 {
     if (!h) return fail(DVC_E_INVALID, "NULL handle");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(sync_all(h));
-    double t = 0.0;
-    for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-        float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
-        t += ms;
-    }
+    HIP_OK(h->sync());
+    hipError_t e = hipSuccess;
+    const double t = dvc_host::ktime_sum(h->ev, h->ev_used, &e);
+    HIP_OK(e);
     if (total_ms) *total_ms = t;
     if (launches) *launches = h->ev_used / 2;
     if (reset) h->ev_used = 0;
@@ -1510,8 +1297,7 @@ void dvc_fd_destroy(dvc_fd* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    (void)sync_all(h);
-    free_all(h);
+    (void)h->sync();
     delete h;
 }
 
@@ -1534,41 +1320,21 @@ int dvc_contour_filter(const uint8_t* mask, int width, int height, int64_t min_a
     dvc::CclBufs::sizes(g, 1, sz);
     c.ptrs(ptrs);
     unsigned long long* stats = nullptr;
-    std::vector<void*> owned;
-    bool oom = false;   // every allocation is checked before any launch
-    auto alloc = [&](void** p, size_t bytes) {
-        *p = nullptr;
-        if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) {
-            *p = nullptr;
-            oom = true;
-            return;
-        }
-        owned.push_back(*p);
-    };
-    for (int i = 0; i < dvc::CclBufs::NARR; ++i) alloc(ptrs[i], sz[i]);
-    alloc((void**)&stats, 8 * 4 * 64);
+    dvc_host::DevMem mem;   // every allocation is checked before any launch; freed on return
+    hipError_t e = mem.alloc(&stats, 8 * 4 * 64);
+    for (int i = 0; i < dvc::CclBufs::NARR && e == hipSuccess; ++i) e = mem.alloc(ptrs[i], sz[i]);
+    if (e != hipSuccess) return fail(DVC_E_NOMEM, "hipMalloc failed");
     c.stats = stats;
-    int rc = DVC_OK;
-    auto done = [&]() { for (void* p : owned) (void)hipFree(p); };
-    if (oom) {
-        done();
-        return fail(DVC_E_NOMEM, "hipMalloc failed");
-    }
     hipStream_t s = nullptr;
-    hipError_t e = hipMemcpy(c.mbits, bits.data(), 8 * H * WW, hipMemcpyHostToDevice);
+    e = hipMemcpy(c.mbits, bits.data(), 8 * H * WW, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(stats, 0, 8 * 4 * 64);
     if (e == hipSuccess) e = hipMemset(c.gpar, 0, sz[6]);
     if (e == hipSuccess) e = dvc::launch_ccl(c, g, 1, min_area2, s);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    unsigned long long st[4] = {0, 0, 0, 0}, slots[64 * 4];
-    if (e == hipSuccess) e = hipMemcpy(bits.data(), c.kbits, 8 * H * WW, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(slots, stats, sizeof(slots), hipMemcpyDeviceToHost);
-    for (int i = 0; i < 64 * 4; ++i) st[i % 4] += slots[i];
-    if (e != hipSuccess) rc = fail(DVC_E_HIP, "contour filter: %s", hipGetErrorString(e));
-    done();
-    if (rc) return rc;
-    for (size_t y = 0; y < H; ++y)
-        for (size_t x = 0; x < W; ++x) filtered[y * W + x] = ((bits[y * WW + x / 64] >> (x % 64)) & 1) ? 255 : 0;
+    unsigned long long st[4];
+    if (e == hipSuccess) e = dvc_host::fold_stats(stats, st);
+    if (e == hipSuccess) e = dvc_host::read_bit_plane(c.kbits, W, H, WW, filtered);   // writes only when it succeeds
+    if (e != hipSuccess) return fail(DVC_E_HIP, "contour filter: %s", hipGetErrorString(e));
     if (components) *components = st[2];
     return DVC_OK;
 }

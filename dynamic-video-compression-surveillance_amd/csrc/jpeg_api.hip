@@ -120,8 +120,8 @@ struct dvc_jpeg {
     int device = -1, max_batch = 1, chan = 3;
     uint32_t flags = 0;
     uint64_t bound = 0;
-    hipStream_t stream = nullptr;   // the caller's (may be NULL = legacy default) or our own
-    bool own_stream = false;
+    dvc_host::HandleStream stream;   // the caller's (may be NULL = legacy default) or our own
+    dvc_host::DevMem mem;
     dvc::JpegTables* d_tab = nullptr;
     dvc::JpegBufs b{};
     // host-pointer mode: staged frames (rows of ip bytes), output slots, sizes
@@ -129,14 +129,6 @@ struct dvc_jpeg {
     uint32_t* d_sizes = nullptr;
     size_t ip = 0;
 };
-
-static void jpeg_free(dvc_jpeg* h)
-{
-    for (void* p : {(void*)h->d_tab, (void*)h->b.levels, (void*)h->b.boff, (void*)h->b.segbits, (void*)h->b.seglen,
-                    (void*)h->b.scratch, (void*)h->b.overflow, (void*)h->d_in, (void*)h->d_out, (void*)h->d_sizes})
-        if (p) (void)hipFree(p);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-}
 
 extern "C" {
 
@@ -176,32 +168,25 @@ int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, 
     hipError_t e = hipSetDevice(device);
     const size_t mb = h->max_batch, nblk = (size_t)g.nseg * g.bps, nseg = g.nseg;
     h->ip = ((size_t)h->chan * g.W + 3) & ~(size_t)3;
-    if (e == hipSuccess) {
-        if (hip_stream || (flags & DVC_FLAG_JOIN_STREAM)) {
-            h->stream = (hipStream_t)hip_stream;
-        } else {
-            e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-            h->own_stream = e == hipSuccess;
-        }
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_tab, sizeof(dvc::JpegTables));
+    dvc_host::DevMem& mem = h->mem;
+    if (e == hipSuccess) e = h->stream.open(hip_stream, flags & DVC_FLAG_JOIN_STREAM);
+    if (e == hipSuccess) e = mem.alloc(&h->d_tab, sizeof(dvc::JpegTables));
     if (e == hipSuccess) e = hipMemcpy(h->d_tab, &h->tab, sizeof(dvc::JpegTables), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.levels, mb * nblk * 64 * sizeof(int16_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.boff, mb * nblk * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.segbits, mb * nseg * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.seglen, mb * nseg * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.scratch, mb * nseg * (size_t)g.segcap);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.overflow, sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(&h->b.levels, mb * nblk * 64 * sizeof(int16_t));
+    if (e == hipSuccess) e = mem.alloc(&h->b.boff, mb * nblk * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(&h->b.segbits, mb * nseg * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(&h->b.seglen, mb * nseg * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(&h->b.scratch, mb * nseg * (size_t)g.segcap);
+    if (e == hipSuccess) e = mem.alloc(&h->b.overflow, sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(h->b.overflow, 0, sizeof(uint32_t));
     if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
-        e = hipMalloc((void**)&h->d_in, mb * h->ip * g.H);   // staged frames
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_out, mb * (size_t)h->bound);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_sizes, mb * sizeof(uint32_t));
+        e = mem.alloc(&h->d_in, mb * h->ip * g.H);   // staged frames
+        if (e == hipSuccess) e = mem.alloc(&h->d_out, mb * (size_t)h->bound);
+        if (e == hipSuccess) e = mem.alloc(&h->d_sizes, mb * sizeof(uint32_t));
     }
     if (e != hipSuccess) {
-        jpeg_free(h);
         delete h;
-        return fail(e == hipErrorOutOfMemory ? DVC_E_NOMEM : DVC_E_HIP, "jpeg create: %s", hipGetErrorString(e));
+        return dvc_host::create_failed(e, "jpeg create");
     }
     *out = h;
     return DVC_OK;
@@ -229,7 +214,7 @@ int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t fra
     if (n > 1 && frame_stride < pitch * (H - 1) + roww) return fail(DVC_E_INVALID, "frame stride invalid");
     HIP_OK(hipSetDevice(h->device));
     const bool devp = h->flags & DVC_FLAG_DEVICE_PTRS;
-    hipStream_t st = h->stream;
+    hipStream_t st = h->stream.s;
     bool overflow = false;
     std::vector<uint32_t> hs((size_t)h->max_batch);
     for (int f0 = 0; f0 < n; f0 += h->max_batch) {
@@ -238,21 +223,8 @@ int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t fra
         uint8_t* o = out + (size_t)f0 * out_stride;
         const uint8_t* kd = in;
         size_t kp = pitch, kfs = frame_stride;
-        if (!devp) {   // frames up, rows of ip bytes: packed frames in one copy each (a 2-D copy of
-                       // pageable memory goes row by row), a packed batch in one
-            const bool packed = pitch == roww && roww == h->ip;
-            if (packed && (m == 1 || frame_stride == roww * H)) {
-                HIP_OK(hipMemcpyAsync(h->d_in, in, (size_t)m * roww * H, hipMemcpyHostToDevice, st));
-            } else {
-                for (int t = 0; t < m; ++t) {
-                    const uint8_t* src = in + (size_t)t * frame_stride;
-                    if (packed)
-                        HIP_OK(hipMemcpyAsync(h->d_in + t * roww * H, src, roww * H, hipMemcpyHostToDevice, st));
-                    else
-                        HIP_OK(hipMemcpy2DAsync(h->d_in + t * h->ip * H, h->ip, src, pitch, roww, H,
-                                                hipMemcpyHostToDevice, st));
-                }
-            }
+        if (!devp) {   // frames up, rows of ip bytes
+            HIP_OK(dvc_host::stage_rows_h2d(h->d_in, h->ip, in, pitch, frame_stride, roww, H, m, st));
             kd = h->d_in;
             kp = h->ip;
             kfs = h->ip * H;
@@ -291,7 +263,7 @@ int dvc_jpeg_sync(dvc_jpeg* h)
     if (!h) return fail(DVC_E_INVALID, "NULL handle");
     if (h->device < 0) return DVC_OK;
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(hipStreamSynchronize(h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream.s));
     if (h->flags & DVC_FLAG_DEVICE_PTRS) {   // an overflow of an asynchronous call is reported here
         uint32_t hov = 0;
         HIP_OK(hipMemcpy(&hov, h->b.overflow, sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -308,8 +280,7 @@ void dvc_jpeg_destroy(dvc_jpeg* h)
     if (!h) return;
     if (h->device >= 0) {
         (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        jpeg_free(h);
+        (void)hipStreamSynchronize(h->stream.s);
     }
     delete h;
 }

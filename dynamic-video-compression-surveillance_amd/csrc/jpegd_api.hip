@@ -23,8 +23,8 @@ struct dvc_jpegd {
     uint32_t flags = 0;
     bool have_header = false, tab_dirty = false;
     dvc::JpegdHeader hdr{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    dvc_host::HandleStream stream;   // the caller's (may be NULL = legacy default) or our own
+    dvc_host::DevMem mem;
     dvc::JpegdTables* d_tab = nullptr;
     dvc::JpegdBufs b{};
     // host-pointer mode: staged samples (slots of in_slot bytes), sizes, packed output frames, statuses
@@ -33,14 +33,6 @@ struct dvc_jpegd {
     int32_t* d_status = nullptr;
     size_t in_slot = 0;
 };
-
-static void jpegd_free(dvc_jpegd* h)
-{
-    for (void* p : {(void*)h->d_tab, (void*)h->b.coef, (void*)h->b.chunkcnt, (void*)h->b.markpos, (void*)h->b.planes,
-                    (void*)h->b.first_err, (void*)h->d_in, (void*)h->d_out, (void*)h->d_sizes, (void*)h->d_status})
-        if (p) (void)hipFree(p);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-}
 
 static size_t up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 
@@ -69,30 +61,23 @@ int dvc_jpegd_create(int max_width, int max_height, int max_batch, int device, v
     *out = nullptr;
     const size_t mb = h->max_batch;
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        if (hip_stream || (flags & DVC_FLAG_JOIN_STREAM)) {
-            h->stream = (hipStream_t)hip_stream;
-        } else {
-            e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-            h->own_stream = e == hipSuccess;
-        }
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_tab, sizeof(dvc::JpegdTables));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.coef, mb * ncoef * sizeof(int16_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.chunkcnt, mb * dvc::kJpegdChunks * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.markpos, mb * nmark * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.planes, mb * ncoef);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->b.first_err, sizeof(int32_t));
+    dvc_host::DevMem& mem = h->mem;
+    if (e == hipSuccess) e = h->stream.open(hip_stream, flags & DVC_FLAG_JOIN_STREAM);
+    if (e == hipSuccess) e = mem.alloc(&h->d_tab, sizeof(dvc::JpegdTables));
+    if (e == hipSuccess) e = mem.alloc(&h->b.coef, mb * ncoef * sizeof(int16_t));
+    if (e == hipSuccess) e = mem.alloc(&h->b.chunkcnt, mb * dvc::kJpegdChunks * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(&h->b.markpos, mb * nmark * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(&h->b.planes, mb * ncoef);
+    if (e == hipSuccess) e = mem.alloc(&h->b.first_err, sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(h->b.first_err, 0, sizeof(int32_t));
     if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
-        e = hipMalloc((void**)&h->d_out, mb * 3 * (size_t)max_width * max_height);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_sizes, mb * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_status, mb * sizeof(int32_t));
+        e = mem.alloc(&h->d_out, mb * 3 * (size_t)max_width * max_height);
+        if (e == hipSuccess) e = mem.alloc(&h->d_sizes, mb * sizeof(uint32_t));
+        if (e == hipSuccess) e = mem.alloc(&h->d_status, mb * sizeof(int32_t));
     }
     if (e != hipSuccess) {
-        jpegd_free(h);
         delete h;
-        return fail(e == hipErrorOutOfMemory ? DVC_E_NOMEM : DVC_E_HIP, "jpegd create: %s", hipGetErrorString(e));
+        return dvc_host::create_failed(e, "jpegd create");
     }
     *out = h;
     return DVC_OK;
@@ -130,7 +115,7 @@ int dvc_jpegd_decode(dvc_jpegd* h, const uint8_t* data, size_t data_stride, cons
     if (pitch < roww) return fail(DVC_E_INVALID, "pitch invalid");
     if (n > 1 && frame_stride < pitch * (H - 1) + roww) return fail(DVC_E_INVALID, "frame stride invalid");
     HIP_OK(hipSetDevice(h->device));
-    hipStream_t st = h->stream;
+    hipStream_t st = h->stream.s;
     if (h->tab_dirty) {   // (pageable source: the runtime has taken its copy when the call returns)
         HIP_OK(hipMemcpyAsync(h->d_tab, &h->hdr.t, sizeof(dvc::JpegdTables), hipMemcpyHostToDevice, st));
         h->tab_dirty = false;
@@ -155,10 +140,10 @@ int dvc_jpegd_decode(dvc_jpegd* h, const uint8_t* data, size_t data_stride, cons
         const size_t slot = up(std::max<size_t>(big, 4), 256);
         if (slot > h->in_slot) {   // the staging area grows to the largest sample seen
             HIP_OK(hipStreamSynchronize(st));
-            if (h->d_in) (void)hipFree(h->d_in);
+            h->mem.release(h->d_in);
             h->d_in = nullptr;
             h->in_slot = 0;
-            const hipError_t e = hipMalloc((void**)&h->d_in, slot * h->max_batch);
+            const hipError_t e = h->mem.alloc(&h->d_in, slot * h->max_batch);
             if (e != hipSuccess) return fail(DVC_E_NOMEM, "jpegd staging: %s", hipGetErrorString(e));
             h->in_slot = slot;
         }
@@ -198,7 +183,7 @@ int dvc_jpegd_sync(dvc_jpegd* h)
     if (!h) return fail(DVC_E_INVALID, "NULL handle");
     if (h->device < 0) return DVC_OK;
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(hipStreamSynchronize(h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream.s));
     if (h->flags & DVC_FLAG_DEVICE_PTRS) {   // a damaged frame of an asynchronous call is reported here, once
         int32_t err = 0;
         HIP_OK(hipMemcpy(&err, h->b.first_err, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -215,8 +200,7 @@ void dvc_jpegd_destroy(dvc_jpegd* h)
     if (!h) return;
     if (h->device >= 0) {
         (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-        jpegd_free(h);
+        (void)hipStreamSynchronize(h->stream.s);
     }
     delete h;
 }

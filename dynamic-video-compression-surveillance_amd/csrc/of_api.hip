@@ -5,7 +5,10 @@
 // lives on the device as per-level polynomial-expansion rings, the raw-mask
 // ring and the per-pixel vote counts. The per-level geometry (pyramid sizes,
 // smoothing kernels, INTER_LINEAR tables, FarnebackPrepareGaussian) is derived
-// here with the same expressions as oracle/of_oracle.c.
+// here with the same expressions as oracle/of_oracle.c. The plumbing shared
+// with the other handles (what a handle owns, stream fork / sync, the frame
+// contract, statistics and bit-plane read-backs) is host_common.h and
+// host_frames.h. Also here: dvc_ofc, compress_with_motion as a handle.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstdio>
@@ -176,7 +179,7 @@ struct dvc_of {
     bool primed = false;
     uint64_t frames = 0;
     int last_n = 0;
-    std::vector<void*> dev;  // every device allocation
+    dvc_host::DevMem mem;    // every device and pinned allocation, every ordering event
     uint8_t *d_in = nullptr, *d_mask = nullptr, *d_cp = nullptr;
     uint8_t *h_in = nullptr, *h_mask = nullptr, *h_cp = nullptr;
     std::vector<hipEvent_t> ev;
@@ -188,49 +191,28 @@ struct dvc_of {
     // strip that polls fails at once and the launch drains; the next sync
     // reports the error (the path a hand-off timeout takes)
     bool fault_abort = false;
+
+    ~dvc_of()
+    {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        for (hipStream_t st : {s_flow, s_mask, stream})
+            if (st) (void)hipStreamDestroy(st);
+    }
+    dvc_host::FrameFmt frame() const { return {fmt, p.width, p.height, crows}; }
+    hipError_t sync() const { return dvc_host::sync_streams({stream, s_flow, s_mask}); }
+    // The caller's stream (if any) -> the internal streams, before a call's work
+    hipError_t wait_user() const
+    {
+        return has_user ? dvc_host::fork_streams(user, ev_user, {stream, s_flow, s_mask}) : hipSuccess;
+    }
 };
 
-static void of_free(dvc_of* h)
-{
-    for (void* p : h->dev)
-        if (p) (void)hipFree(p);
-    h->dev.clear();
-    for (void* p : {(void*)h->h_in, (void*)h->h_mask, (void*)h->h_cp})
-        if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    for (OfSlot& sl : h->slot)
-        for (hipEvent_t e : {sl.ev_pyr, sl.ev_flow, sl.ev_mask, sl.ev_l1, sl.ev_l0a})
-            if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {h->ev_user, h->ev_join, h->ev_gray, h->ev_side})
-        if (e) (void)hipEventDestroy(e);
-    for (hipStream_t st : {h->s_flow, h->s_mask, h->stream})
-        if (st) (void)hipStreamDestroy(st);
-}
-
-// The caller's stream (if any) -> the internal streams, before a call's work;
-// the internal streams -> the caller's stream after it (outputs on s_mask).
-static hipError_t of_wait_user(dvc_of* h)
-{
-    if (!h->has_user) return hipSuccess;
-    hipError_t e = hipEventRecord(h->ev_user, h->user);
-    for (hipStream_t st : {h->stream, h->s_flow, h->s_mask})
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, h->ev_user, 0);
-    return e;
-}
-
+// The internal streams -> the caller's stream after a call (outputs on s_mask).
 static hipError_t of_join_user(dvc_of* h)
 {
     if (!h->has_user) return hipSuccess;
     hipError_t e = hipEventRecord(h->ev_join, h->s_mask);
     if (e == hipSuccess) e = hipStreamWaitEvent(h->user, h->ev_join, 0);
-    return e;
-}
-
-static hipError_t of_sync_all(dvc_of* h)
-{
-    hipError_t e = hipStreamSynchronize(h->stream);
-    for (hipStream_t st : {h->s_flow, h->s_mask})
-        if (e == hipSuccess && st) e = hipStreamSynchronize(st);
     return e;
 }
 
@@ -243,68 +225,30 @@ static int of_check_abort(dvc_of* h)
     return DVC_OK;
 }
 
-template <typename T>
-static hipError_t of_alloc(dvc_of* h, T** p, size_t bytes)
-{
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-    if (e == hipSuccess) {
-        h->dev.push_back(q);
-        *p = reinterpret_cast<T*>(q);
-    }
-    return e;
-}
-
 extern "C" {
 
-// Frames handed to prime/step: BGR rows of `pitch` (>= 3W), or 4:2:0
-// surfaces (luma pitch >= W; I420: even).
-static bool of_pitch_ok(const dvc_of* h, size_t pitch)
-{
-    const size_t W = h->p.width;
-    if (h->fmt == DVC_FMT_BGR) return pitch >= 3 * W;
-    return pitch >= W && (h->fmt != DVC_FMT_I420 || pitch % 2 == 0);
-}
-
-// Can the kernels read these BGR device frames in place? Dword rows reaching
-// whole 4-px quads (3 * roundup(W, 4) bytes), aligned base and frame stride;
-// anything else is re-pitched into the slot's staging frames first. W % 4 == 0:
-// a frame's last row then ends exactly at its last quad, so a buffer sized to
-// the frame span (pitch * (H - 1) + 3W, what the step checks) is never read
-// past its end.
-static bool of_direct(const dvc_of* h, const uint8_t* p, size_t pitch, size_t fstride, int n)
-{
-    return h->p.width % 4 == 0 && pitch % 4 == 0 && pitch >= (size_t)h->ip && ((uintptr_t)p & 3) == 0 &&
-           (n <= 1 || fstride % 4 == 0);
-}
-
-// Can k_of_front0 / k_of_out read these 4:2:0 surfaces in place? Dword luma
-// rows (pitch % 4 == 0, so rows reach whole quads), aligned base and stride,
-// W % 4 == 0 (the last luma and chroma rows end at a whole quad's bytes).
-// DVC_OF_YUV_DIRECT=0 forces the staged conversion (A/B).
-static bool of_direct_yuv(const dvc_of* h, const uint8_t* p, size_t pitch, size_t fstride, int n)
-{
-    static const int on = [] { const char* e = dvc::tune_env("DVC_OF_YUV_DIRECT"); return e ? atoi(e) : 1; }();
-    return on && h->p.width % 4 == 0 && pitch % 4 == 0 && ((uintptr_t)p & 3) == 0 && (n <= 1 || fstride % 4 == 0);
-}
-
 // The frames the kernels read for a batch in slot S: the caller's device
-// frames in place (BGR rows the kernels can read, or 4:2:0 surfaces converted
-// per pixel as they load: *sf says which), or (re-pitch needed, surfaces not
-// readable in place) converted / copied into S.fin on stream `st` once the
-// slot's previous batch is done with it.
+// frames in place (BGR rows the kernels can read, reaching whole 4-px quads:
+// 3 * roundup(W, 4) bytes; or 4:2:0 surfaces converted per pixel as they load
+// — DVC_OF_YUV_DIRECT=0 forces the staged conversion, A/B; *sf says which), or
+// (host_frames.h readable_in_place says no) converted / copied into S.fin on
+// stream `st` once the slot's previous batch is done with it.
 static int of_stage(dvc_of* h, OfSlot& S, const uint8_t* d, int dp, size_t fstride, int n, int crows, hipStream_t st,
                     const uint8_t** kd, int* kp, size_t* kfs, dvc::SrcFmt* sf)
 {
+    static const int yuv_direct = [] { const char* e = dvc::tune_env("DVC_OF_YUV_DIRECT"); return e ? atoi(e) : 1; }();
     const size_t W = h->p.width, H = h->p.height, FS = (size_t)h->ip * H;
+    const bool bgr = h->fmt == DVC_FMT_BGR;
+    const bool direct = (bgr || yuv_direct) &&
+                        dvc_host::readable_in_place(h->p.width, d, (size_t)dp, bgr ? (size_t)h->ip : 0, fstride, n);
     *sf = dvc::SrcFmt{DVC_FMT_BGR, 0, 0, 0};
-    if (h->fmt == DVC_FMT_BGR && of_direct(h, d, (size_t)dp, fstride, n)) {
+    if (bgr && direct) {
         *kd = d;
         *kp = dp;
         *kfs = fstride;
         return DVC_OK;
     }
-    if (h->fmt != DVC_FMT_BGR && of_direct_yuv(h, d, (size_t)dp, fstride, n)) {
+    if (direct) {
         const dvc::YuvLayout L = dvc::yuv_layout(d, dp, h->fmt, crows, fstride);
         *sf = dvc::SrcFmt{h->fmt, L.uoff, L.voff, L.cpitch};
         *kd = d;
@@ -312,7 +256,7 @@ static int of_stage(dvc_of* h, OfSlot& S, const uint8_t* d, int dp, size_t fstri
         *kfs = fstride;
         return DVC_OK;
     }
-    if (!S.fin) HIP_OK(of_alloc(h, &S.fin, FS * h->max_batch));
+    if (!S.fin) HIP_OK(h->mem.alloc(&S.fin, FS * h->max_batch));
     if (S.recorded) HIP_OK(hipStreamWaitEvent(st, S.ev_mask, 0));   // batch i-2's k_of_out read S.fin
     if (h->fmt != DVC_FMT_BGR) {   // cvtColor of the decoded surfaces (what cap.read() returns, of:54,66)
         HIP_OK(dvc::launch_yuv420_to_bgr(dvc::yuv_layout(d, dp, h->fmt, crows, fstride), (int)W, (int)H, n, S.fin,
@@ -327,31 +271,6 @@ static int of_stage(dvc_of* h, OfSlot& S, const uint8_t* d, int dp, size_t fstri
     *kp = h->ip;
     *kfs = FS;
     return DVC_OK;
-}
-
-static size_t of_frame_span(const dvc_of* h, size_t pitch)
-{
-    if (h->fmt == DVC_FMT_BGR) return pitch * (h->p.height - 1) + 3 * (size_t)h->p.width;
-    return dvc::yuv_frame_bytes(pitch, h->crows);
-}
-
-// A host frame into pinned staging in the layout the device copy is read with
-// (BGR rows of ip; YUV: luma rows of W and the chroma plane(s) right after).
-static void of_pack_host(const dvc_of* h, const uint8_t* src, size_t pitch, uint8_t* dst)
-{
-    const size_t W = h->p.width, H = h->p.height;
-    if (h->fmt == DVC_FMT_BGR) {
-        for (size_t y = 0; y < H; ++y) std::memcpy(dst + y * h->ip, src + y * pitch, 3 * W);
-        return;
-    }
-    const dvc::YuvLayout L = dvc::yuv_layout(src, pitch, h->fmt, h->crows, 0);
-    const dvc::YuvLayout C = dvc::yuv_layout(dst, W, h->fmt, (int)H, 0);
-    for (size_t y = 0; y < H; ++y) std::memcpy(dst + y * W, src + y * pitch, W);
-    const size_t cb = h->fmt == DVC_FMT_NV12 ? W : W / 2;
-    for (size_t y = 0; y < H / 2; ++y) {
-        std::memcpy(dst + C.uoff + y * C.cpitch, src + L.uoff + y * L.cpitch, cb);
-        if (h->fmt == DVC_FMT_I420) std::memcpy(dst + C.voff + y * C.cpitch, src + L.voff + y * L.cpitch, cb);
-    }
 }
 
 int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of** out)
@@ -434,16 +353,12 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
     }
 
     auto bad = [&](hipError_t e, const char* what) {
-        int rc = fail(e == hipErrorOutOfMemory ? DVC_E_NOMEM : DVC_E_HIP, "%s: %s", what, hipGetErrorString(e));
-        of_free(h);
         delete h;
-        return rc;
+        return dvc_host::create_failed(e, what);
     };
     auto unsupported = [&](const char* what, int v) {
-        int rc = fail(DVC_E_UNSUPPORTED, what, v);
-        of_free(h);
         delete h;
-        return rc;
+        return fail(DVC_E_UNSUPPORTED, what, v);
     };
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return bad(e, "hipSetDevice");
@@ -457,7 +372,7 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
     // mask high / pyramid low 15.88 k Mpx/s)
     if ((e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess) return bad(e, "hipStreamCreate");
     for (hipEvent_t* ev : {&h->ev_user, &h->ev_join, &h->ev_gray, &h->ev_side})
-        if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+        if ((e = h->mem.event(ev)) != hipSuccess) return bad(e, "hipEventCreate");
     h->s_pyr = h->stream;
     {
         // DVC_OF_PRIO=<flow><mask> (experiments): h / n / l stream priority each
@@ -475,7 +390,7 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
     }
     for (OfSlot& sl : h->slot)
         for (hipEvent_t* ev : {&sl.ev_pyr, &sl.ev_flow, &sl.ev_mask, &sl.ev_l1, &sl.ev_l0a})
-            if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+            if ((e = h->mem.event(ev)) != hipSuccess) return bad(e, "hipEventCreate");
     const size_t W = p.width, H = p.height, N = W * H, WW = g.WW, CAP = g.CAP;
     // levels (oc_fb_level_poly geometry)
     std::vector<dvc::LinTap> tabs;   // all tables, uploaded once
@@ -538,7 +453,7 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
         }
     }
     dvc::LinTap* dtab = nullptr;
-    if ((e = of_alloc(h, &dtab, sizeof(dvc::LinTap) * tabs.size())) != hipSuccess) return bad(e, "hipMalloc");
+    if ((e = h->mem.alloc(&dtab, sizeof(dvc::LinTap) * tabs.size())) != hipSuccess) return bad(e, "hipMalloc");
     if ((e = hipMemcpy(dtab, tabs.data(), sizeof(dvc::LinTap) * tabs.size(), hipMemcpyHostToDevice)) != hipSuccess)
         return bad(e, "hipMemcpy");
     for (int k = 0; k <= L; ++k) {
@@ -548,11 +463,11 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
         lv.yt = dtab + tr[k].yt;
         lv.ux = k < L ? dtab + tr[k].ux : nullptr;
         lv.uy = k < L ? dtab + tr[k].uy : nullptr;
-        if ((e = of_alloc(h, &lv.R, 20 * px * g.RS)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&lv.R, 20 * px * g.RS)) != hipSuccess) return bad(e, "hipMalloc");
         for (int q = 0; q < 2; ++q)
-            if ((e = of_alloc(h, &lv.flow[q], 8 * px * mb)) != hipSuccess) return bad(e, "hipMalloc");
-        if (k > 0 && (e = of_alloc(h, &lv.tmpc, 4 * H * 2 * (size_t)lv.w * mb)) != hipSuccess) return bad(e, "hipMalloc");
-        if (k > 0 && (e = of_alloc(h, &lv.vtmp, 4 * 2 * (size_t)lv.h * 2 * lv.w * mb)) != hipSuccess)
+            if ((e = h->mem.alloc(&lv.flow[q], 8 * px * mb)) != hipSuccess) return bad(e, "hipMalloc");
+        if (k > 0 && (e = h->mem.alloc(&lv.tmpc, 4 * H * 2 * (size_t)lv.w * mb)) != hipSuccess) return bad(e, "hipMalloc");
+        if (k > 0 && (e = h->mem.alloc(&lv.vtmp, 4 * 2 * (size_t)lv.h * 2 * lv.w * mb)) != hipSuccess)
             return bad(e, "hipMalloc");
     }
     dvc::OfBufs& b = h->b;
@@ -579,14 +494,14 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
         {(void**)&b.scan_abort, 4},
     };
     for (auto& a : allocs)
-        if ((e = of_alloc(h, a.ptr, a.bytes)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(a.ptr, a.bytes)) != hipSuccess) return bad(e, "hipMalloc");
     if (p.flags & DVC_FLAG_KEEP_PLANES)
-        if ((e = of_alloc(h, &b.dbg_flow, 8 * N)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&b.dbg_flow, 8 * N)) != hipSuccess) return bad(e, "hipMalloc");
     if (g.sliding) {   // k_flow_scan hand-off slots, sized for the largest level
         size_t slots = 0;
         for (int k = 0; k <= L; ++k) slots = std::max(slots, dvc::of_scan_slots(g, h->lv[k].w, h->lv[k].h));
         // tags start at 0, below every launch's epoch (>= 1): no slot reads as published
-        if ((e = of_alloc(h, &b.scan_g, 16 * slots * mb)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&b.scan_g, 16 * slots * mb)) != hipSuccess) return bad(e, "hipMalloc");
         if ((e = hipMemset(b.scan_g, 0, 16 * slots * mb)) != hipSuccess) return bad(e, "hipMemset");
     }
     if ((e = hipMemset(b.scan_abort, 0, 4)) != hipSuccess) return bad(e, "hipMemset");
@@ -601,15 +516,15 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
     const size_t FS = (size_t)h->ip * H;   // one staged / packed BGR frame
     if (h->fmt != DVC_FMT_BGR)   // BGR device frames: allocated on first use (of_stage), when re-pitched
         for (OfSlot& sl : h->slot)
-            if ((e = of_alloc(h, &sl.fin, FS * mb)) != hipSuccess) return bad(e, "hipMalloc");
+            if ((e = h->mem.alloc(&sl.fin, FS * mb)) != hipSuccess) return bad(e, "hipMalloc");
     if (!(p.flags & DVC_FLAG_DEVICE_PTRS)) {
         const size_t FI = h->fmt == DVC_FMT_BGR ? FS : 3 * N;   // packed host frame (YUV: 1.5 N bytes used)
-        if ((e = of_alloc(h, &h->d_in, FI * mb)) != hipSuccess) return bad(e, "hipMalloc");
-        if ((e = of_alloc(h, &h->d_mask, N * mb)) != hipSuccess) return bad(e, "hipMalloc");
-        if ((e = of_alloc(h, &h->d_cp, 3 * N * mb)) != hipSuccess) return bad(e, "hipMalloc");
-        if ((e = hipHostMalloc((void**)&h->h_in, FI * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
-        if ((e = hipHostMalloc((void**)&h->h_mask, N * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
-        if ((e = hipHostMalloc((void**)&h->h_cp, 3 * N * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
+        if ((e = h->mem.alloc(&h->d_in, FI * mb)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&h->d_mask, N * mb)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&h->d_cp, 3 * N * mb)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc_pinned(&h->h_in, FI * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
+        if ((e = h->mem.alloc_pinned(&h->h_mask, N * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
+        if ((e = h->mem.alloc_pinned(&h->h_cp, 3 * N * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
     }
     if ((e = hipMemsetAsync(b.stats, 0, 8 * 4 * 64, h->stream)) != hipSuccess) return bad(e, "hipMemset");
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return bad(e, "hipStreamSynchronize");
@@ -620,15 +535,15 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
 int dvc_of_prime(dvc_of* h, const uint8_t* bgr, size_t pitch)
 {
     if (!h || !bgr) return fail(DVC_E_INVALID, "NULL argument");
-    if (!of_pitch_ok(h, pitch)) return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
+    if (!dvc_host::pitch_ok(h->frame(), pitch)) return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(of_sync_all(h));   // no batch of a previous run may still be in flight
-    HIP_OK(of_wait_user(h));
+    HIP_OK(h->sync());   // no batch of a previous run may still be in flight
+    HIP_OK(h->wait_user());
     const size_t W = h->p.width, H = h->p.height, WW = h->g.WW;
     const uint8_t* d = bgr;
     int dp = (int)pitch, crows = h->crows;
     if (!(h->p.flags & DVC_FLAG_DEVICE_PTRS)) {
-        of_pack_host(h, bgr, pitch, h->h_in);
+        dvc_host::pack_host_frame(h->frame(), bgr, pitch, h->h_in, h->ip);
         const size_t fb = h->fmt == DVC_FMT_BGR ? (size_t)h->ip * H : dvc::yuv_frame_bytes(W, (int)H);
         HIP_OK(hipMemcpyAsync(h->d_in, h->h_in, fb, hipMemcpyHostToDevice, h->stream));
         d = h->d_in;
@@ -671,8 +586,8 @@ int dvc_of_set_state(dvc_of* h, const uint8_t* prev_gray, const uint8_t* raw_mas
 {
     if (!h || !prev_gray || (n > 0 && !raw_masks) || n < 0) return fail(DVC_E_INVALID, "NULL argument / bad count");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(of_sync_all(h));
-    HIP_OK(of_wait_user(h));
+    HIP_OK(h->sync());
+    HIP_OK(h->wait_user());
     const size_t W = h->p.width, H = h->p.height, WW = h->g.WW, window = (size_t)h->p.window;
     if ((size_t)n > window) {
         raw_masks += ((size_t)n - window) * W * H;
@@ -687,7 +602,7 @@ int dvc_of_set_state(dvc_of* h, const uint8_t* prev_gray, const uint8_t* raw_mas
             p[0] = p[1] = p[2] = g;
         }
     uint8_t* d = nullptr;
-    HIP_OK(of_alloc(h, &d, bgr.size()));
+    HIP_OK(h->mem.alloc(&d, bgr.size()));
     HIP_OK(hipMemcpy(d, bgr.data(), bgr.size(), hipMemcpyHostToDevice));
     // frames 1..n are the window's masks; the previous frame is a = n
     std::vector<uint64_t> bits(H * WW * std::max(n, 1), 0);
@@ -710,12 +625,7 @@ int dvc_of_set_state(dvc_of* h, const uint8_t* prev_gray, const uint8_t* raw_mas
     HIP_OK(hipMemsetAsync(h->b.scan_abort, 0, 4, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));
     // the temporary frame is released now (no kernel reads it any more)
-    for (size_t i = 0; i < h->dev.size(); ++i)
-        if (h->dev[i] == d) {
-            (void)hipFree(d);
-            h->dev.erase(h->dev.begin() + (long)i);
-            break;
-        }
+    h->mem.release(d);
     h->seq = 0;
     h->a_next = n + 1;
     h->frames = 0;
@@ -833,12 +743,12 @@ static int of_run(dvc_of* h, const uint8_t* bgr, size_t pitch, size_t fstride, i
     if (n < 0) return fail(DVC_E_INVALID, "negative frame count");
     const size_t W = h->p.width, H = h->p.height, N = W * H;
     const bool yuv = h->fmt != DVC_FMT_BGR;
-    if (!of_pitch_ok(h, pitch)) return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
-    if (n > 1 && fstride < of_frame_span(h, pitch)) return fail(DVC_E_INVALID, "frame stride %zu invalid", fstride);
+    if (!dvc_host::pitch_ok(h->frame(), pitch)) return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
+    if (n > 1 && fstride < dvc_host::frame_span(h->frame(), pitch)) return fail(DVC_E_INVALID, "frame stride %zu invalid", fstride);
     if (n > 1 && mask && mstride < N) return fail(DVC_E_INVALID, "mask stride %zu invalid", mstride);
     if (n > 1 && compressed && ostride < 3 * N) return fail(DVC_E_INVALID, "output frame stride %zu invalid", ostride);
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(of_wait_user(h));
+    HIP_OK(h->wait_user());
     const bool devp = h->p.flags & DVC_FLAG_DEVICE_PTRS;
     for (int f0 = 0; f0 < n; f0 += h->max_batch) {
         const int m = std::min(h->max_batch, n - f0);
@@ -850,15 +760,16 @@ static int of_run(dvc_of* h, const uint8_t* bgr, size_t pitch, size_t fstride, i
             if (rc) return rc;
             continue;
         }
-        const size_t FI = yuv ? 3 * N : (size_t)h->ip * H;   // packed frame slot (of_pack_host)
-        for (int t = 0; t < m; ++t) of_pack_host(h, in + (size_t)t * fstride, pitch, h->h_in + (size_t)t * FI);
+        const size_t FI = yuv ? 3 * N : (size_t)h->ip * H;   // packed frame slot (pack_host_frame)
+        for (int t = 0; t < m; ++t)
+            dvc_host::pack_host_frame(h->frame(), in + (size_t)t * fstride, pitch, h->h_in + (size_t)t * FI, h->ip);
         HIP_OK(hipMemcpyAsync(h->d_in, h->h_in, (size_t)m * FI, hipMemcpyHostToDevice, h->s_pyr));
         int rc = of_enqueue(h, h->d_in, (int)(yuv ? W : h->ip), FI, m, mk ? h->d_mask : nullptr, N,
                             cp ? h->d_cp : nullptr, 3 * N, (int)H);
         if (rc) return rc;
         if (mk) HIP_OK(hipMemcpyAsync(h->h_mask, h->d_mask, (size_t)m * N, hipMemcpyDeviceToHost, h->s_mask));
         if (cp) HIP_OK(hipMemcpyAsync(h->h_cp, h->d_cp, (size_t)m * 3 * N, hipMemcpyDeviceToHost, h->s_mask));
-        HIP_OK(of_sync_all(h));
+        HIP_OK(h->sync());
         for (int t = 0; t < m; ++t) {
             if (mk) std::memcpy(mk + (size_t)t * mstride, h->h_mask + (size_t)t * N, N);
             if (cp) std::memcpy(cp + (size_t)t * ostride, h->h_cp + (size_t)t * 3 * N, 3 * N);
@@ -885,7 +796,7 @@ int dvc_of_sync(dvc_of* h)
 {
     if (!h) return fail(DVC_E_INVALID, "NULL handle");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(of_sync_all(h));
+    HIP_OK(h->sync());
     return of_check_abort(h);
 }
 
@@ -893,10 +804,9 @@ int dvc_of_get_stats(dvc_of* h, dvc_of_stats* out)
 {
     if (!h || !out) return fail(DVC_E_INVALID, "NULL argument");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(of_sync_all(h));
-    unsigned long long slots[64 * 4], s[4] = {0, 0, 0, 0};
-    HIP_OK(hipMemcpy(slots, h->b.stats, sizeof(slots), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 64 * 4; ++i) s[i % 4] += slots[i];
+    HIP_OK(h->sync());
+    unsigned long long s[4];
+    HIP_OK(dvc_host::fold_stats(h->b.stats, s));
     out->frames = h->frames;
     out->motion_px = s[1];
     out->components = s[2];
@@ -909,8 +819,8 @@ int dvc_of_read_plane(dvc_of* h, int plane, uint8_t* dst)
     if (!h || !dst) return fail(DVC_E_INVALID, "NULL argument");
     if (!h->frames) return fail(DVC_E_STATE, "no frame stepped yet");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(of_sync_all(h));
-    const size_t W = h->p.width, H = h->p.height, N = W * H, WW = h->g.WW, t = (size_t)h->last_n - 1;
+    HIP_OK(h->sync());
+    const size_t W = h->p.width, H = h->p.height, WW = h->g.WW, t = (size_t)h->last_n - 1;
     if (plane == DVC_OF_PLANE_GRAY) {   // rows of GP on the device
         const size_t GP = h->g.GP;
         HIP_OK(hipMemcpy2D(dst, W, h->b.gray + t * GP * H, GP, W, H, hipMemcpyDeviceToHost));
@@ -924,10 +834,7 @@ int dvc_of_read_plane(dvc_of* h, int plane, uint8_t* dst)
     case DVC_OF_PLANE_RECT: src = h->b.rbits + t * H * WW; break;
     default: return fail(DVC_E_INVALID, "unknown plane %d", plane);
     }
-    std::vector<uint64_t> bits(H * WW);
-    HIP_OK(hipMemcpy(bits.data(), src, 8 * H * WW, hipMemcpyDeviceToHost));
-    for (size_t y = 0; y < H; ++y)
-        for (size_t x = 0; x < W; ++x) dst[y * W + x] = ((bits[y * WW + x / 64] >> (x % 64)) & 1) ? 255 : 0;
+    HIP_OK(dvc_host::read_bit_plane(src, W, H, WW, dst));
     return DVC_OK;
 }
 
@@ -937,7 +844,7 @@ int dvc_of_read_flow(dvc_of* h, float* dst)
     if (!h->frames) return fail(DVC_E_STATE, "no frame stepped yet");
     if (!h->b.dbg_flow) return fail(DVC_E_STATE, "flow readback needs DVC_FLAG_KEEP_PLANES");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(of_sync_all(h));
+    HIP_OK(h->sync());
     HIP_OK(hipMemcpy(dst, h->b.dbg_flow, 8 * (size_t)h->p.width * h->p.height, hipMemcpyDeviceToHost));
     return DVC_OK;
 }
@@ -946,13 +853,10 @@ int dvc_of_ktime(dvc_of* h, double* total_ms, uint64_t* launches, int reset)
 {
     if (!h) return fail(DVC_E_INVALID, "NULL handle");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(of_sync_all(h));
-    double t = 0.0;
-    for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-        float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
-        t += ms;
-    }
+    HIP_OK(h->sync());
+    hipError_t e = hipSuccess;
+    const double t = dvc_host::ktime_sum(h->ev, h->ev_used, &e);
+    HIP_OK(e);
     if (total_ms) *total_ms = t;
     if (launches) *launches = (h->ev_used / 2) * (uint64_t)h->g.iters;
     if (reset) h->ev_used = 0;
@@ -976,7 +880,7 @@ int dvc_of_debug_read(dvc_of* h, int what, int level, void* dst, int* w, int* hg
     if (!dst) return DVC_OK;
     if (!h->frames) return fail(DVC_E_STATE, "no frame stepped yet");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(of_sync_all(h));
+    HIP_OK(h->sync());
     const size_t px = (size_t)L.w * L.h;
     const long long a = h->a_next - 1;
     const void* src = nullptr;
@@ -1005,8 +909,7 @@ void dvc_of_destroy(dvc_of* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    (void)of_sync_all(h);
-    of_free(h);
+    (void)h->sync();
     delete h;
 }
 
@@ -1019,19 +922,12 @@ struct dvc_ofc {
     int W = 0, H = 0, WW = 0, ip = 0, device = 0, max_batch = 1;
     uint32_t flags = 0;
     float quant = 100.f;
-    hipStream_t stream = nullptr;    // the caller's (may be NULL = legacy default) or our own
-    bool own_stream = false;
+    dvc_host::HandleStream stream;   // the caller's, or our own when create's hip_stream is NULL
+    dvc_host::DevMem mem;
     uint8_t *fin = nullptr, *d_mask = nullptr, *d_out = nullptr;
     uint64_t* bits = nullptr;
     dvc::DctMat M{};
 };
-
-static void ofc_free(dvc_ofc* h)
-{
-    for (void* p : {(void*)h->fin, (void*)h->d_mask, (void*)h->d_out, (void*)h->bits})
-        if (p) (void)hipFree(p);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-}
 
 extern "C" {
 
@@ -1055,23 +951,17 @@ int dvc_ofc_create(int width, int height, float quant, int max_batch, int device
     h->quant = quant;
     dvc_host::dct_matrix(8, h->M);
     const size_t W = width, H = height, mb = h->max_batch;
-    hipError_t e = hipSuccess;
-    if (hip_stream) {
-        h->stream = (hipStream_t)hip_stream;
-    } else {
-        e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-        h->own_stream = e == hipSuccess;
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&h->bits, 8 * H * h->WW * mb);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->fin, (size_t)h->ip * H * mb);   // staged / re-pitched frames
+    // (a NULL hip_stream always means a stream of our own: DVC_FLAG_JOIN_STREAM is not looked at)
+    hipError_t e = h->stream.open(hip_stream, false);
+    if (e == hipSuccess) e = h->mem.alloc(&h->bits, 8 * H * h->WW * mb);
+    if (e == hipSuccess) e = h->mem.alloc(&h->fin, (size_t)h->ip * H * mb);   // staged / re-pitched frames
     if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
-        e = hipMalloc((void**)&h->d_mask, 3 * W * H * mb);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_out, 3 * W * H * mb);
+        e = h->mem.alloc(&h->d_mask, 3 * W * H * mb);
+        if (e == hipSuccess) e = h->mem.alloc(&h->d_out, 3 * W * H * mb);
     }
     if (e != hipSuccess) {
-        ofc_free(h);
         delete h;
-        return fail(e == hipErrorOutOfMemory ? DVC_E_NOMEM : DVC_E_HIP, "ofc create: %s", hipGetErrorString(e));
+        return dvc_host::create_failed(e, "ofc create");
     }
     *out = h;
     return DVC_OK;
@@ -1090,7 +980,7 @@ int dvc_ofc_run(dvc_ofc* h, const uint8_t* bgr, size_t pitch, size_t frame_strid
         return fail(DVC_E_INVALID, "frame / mask / output stride invalid");
     HIP_OK(hipSetDevice(h->device));
     const bool devp = h->flags & DVC_FLAG_DEVICE_PTRS;
-    hipStream_t st = h->stream;
+    hipStream_t st = h->stream.s;
     dvc::OfGeom g{};
     g.W = h->W;
     g.H = h->H;
@@ -1150,7 +1040,7 @@ int dvc_ofc_sync(dvc_ofc* h)
 {
     if (!h) return fail(DVC_E_INVALID, "NULL handle");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(hipStreamSynchronize(h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream.s));
     return DVC_OK;
 }
 
@@ -1158,8 +1048,7 @@ void dvc_ofc_destroy(dvc_ofc* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    ofc_free(h);
+    (void)hipStreamSynchronize(h->stream.s);
     delete h;
 }
 

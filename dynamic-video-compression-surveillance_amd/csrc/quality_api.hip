@@ -15,41 +15,14 @@ struct dvc_quality {
     dvc::QualityGeom g{};
     int device = -1, max_batch = 1;
     uint32_t flags = 0;
-    hipStream_t stream = nullptr;   // the caller's (may be NULL = legacy default) or our own
-    bool own_stream = false;
+    dvc_host::HandleStream stream;   // the caller's (may be NULL = legacy default) or our own
+    dvc_host::DevMem mem;
     uint64_t* d_part = nullptr;     // five words per tile and frame
     // host-pointer mode: both staged batches (rows of ip bytes) and the records
     uint8_t *d_a = nullptr, *d_b = nullptr;
     dvc::QualityFrame* d_res = nullptr;
     size_t ip = 0;
 };
-
-static void quality_free(dvc_quality* h)
-{
-    for (void* p : {(void*)h->d_part, (void*)h->d_a, (void*)h->d_b, (void*)h->d_res})
-        if (p) (void)hipFree(p);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-}
-
-// n host frames up into rows of h->ip bytes: packed frames in one copy each (a
-// 2-D copy of pageable memory goes row by row), a packed batch in one.
-static int stage(dvc_quality* h, uint8_t* dst, const uint8_t* src, size_t pitch, size_t stride, int n)
-{
-    const size_t roww = 3 * (size_t)h->g.W, H = h->g.H;
-    const bool packed = pitch == roww && roww == h->ip;
-    if (packed && (n == 1 || stride == roww * H)) {
-        HIP_OK(hipMemcpyAsync(dst, src, (size_t)n * roww * H, hipMemcpyHostToDevice, h->stream));
-        return DVC_OK;
-    }
-    for (int t = 0; t < n; ++t) {
-        const uint8_t* s = src + (size_t)t * stride;
-        if (packed)
-            HIP_OK(hipMemcpyAsync(dst + t * roww * H, s, roww * H, hipMemcpyHostToDevice, h->stream));
-        else
-            HIP_OK(hipMemcpy2DAsync(dst + t * h->ip * H, h->ip, s, pitch, roww, H, hipMemcpyHostToDevice, h->stream));
-    }
-    return DVC_OK;
-}
 
 extern "C" {
 
@@ -72,24 +45,16 @@ int dvc_quality_create(int width, int height, int max_batch, int device, void* h
     h->ip = (3 * (size_t)width + 3) & ~(size_t)3;
     const size_t mb = max_batch, tiles = (size_t)h->g.tiles_x * h->g.tiles_y;
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) {
-        if (hip_stream || (flags & DVC_FLAG_JOIN_STREAM)) {
-            h->stream = (hipStream_t)hip_stream;
-        } else {
-            e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-            h->own_stream = e == hipSuccess;
-        }
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_part, mb * tiles * 5 * sizeof(uint64_t));
+    if (e == hipSuccess) e = h->stream.open(hip_stream, flags & DVC_FLAG_JOIN_STREAM);
+    if (e == hipSuccess) e = h->mem.alloc(&h->d_part, mb * tiles * 5 * sizeof(uint64_t));
     if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
-        e = hipMalloc((void**)&h->d_a, mb * h->ip * height);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_b, mb * h->ip * height);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_res, mb * sizeof(dvc::QualityFrame));
+        e = h->mem.alloc(&h->d_a, mb * h->ip * height);
+        if (e == hipSuccess) e = h->mem.alloc(&h->d_b, mb * h->ip * height);
+        if (e == hipSuccess) e = h->mem.alloc(&h->d_res, mb * sizeof(dvc::QualityFrame));
     }
     if (e != hipSuccess) {
-        quality_free(h);
         delete h;
-        return fail(e == hipErrorOutOfMemory ? DVC_E_NOMEM : DVC_E_HIP, "quality create: %s", hipGetErrorString(e));
+        return dvc_host::create_failed(e, "quality create");
     }
     *out = h;
     return DVC_OK;
@@ -109,15 +74,15 @@ int dvc_quality_compare(dvc_quality* h, const uint8_t* ref, size_t ref_pitch, si
     if (h->flags & DVC_FLAG_DEVICE_PTRS) {
         if ((uintptr_t)results & 7) return fail(DVC_E_INVALID, "results must be 8-byte aligned");
         HIP_OK(dvc::quality_launch(ref, ref_pitch, ref_stride, test, test_pitch, test_stride, n, h->g, h->d_part, res,
-                                   h->stream));
+                                   h->stream.s));
         return DVC_OK;
     }
-    if (int rc = stage(h, h->d_a, ref, ref_pitch, ref_stride, n)) return rc;
-    if (int rc = stage(h, h->d_b, test, test_pitch, test_stride, n)) return rc;
+    HIP_OK(dvc_host::stage_rows_h2d(h->d_a, h->ip, ref, ref_pitch, ref_stride, roww, H, n, h->stream.s));
+    HIP_OK(dvc_host::stage_rows_h2d(h->d_b, h->ip, test, test_pitch, test_stride, roww, H, n, h->stream.s));
     HIP_OK(dvc::quality_launch(h->d_a, h->ip, h->ip * H, h->d_b, h->ip, h->ip * H, n, h->g, h->d_part, h->d_res,
-                               h->stream));
-    HIP_OK(hipMemcpyAsync(res, h->d_res, n * sizeof(dvc::QualityFrame), hipMemcpyDeviceToHost, h->stream));
-    HIP_OK(hipStreamSynchronize(h->stream));
+                               h->stream.s));
+    HIP_OK(hipMemcpyAsync(res, h->d_res, n * sizeof(dvc::QualityFrame), hipMemcpyDeviceToHost, h->stream.s));
+    HIP_OK(hipStreamSynchronize(h->stream.s));
     return DVC_OK;
 }
 
@@ -125,7 +90,7 @@ int dvc_quality_sync(dvc_quality* h)
 {
     if (!h) return fail(DVC_E_INVALID, "NULL handle");
     HIP_OK(hipSetDevice(h->device));
-    HIP_OK(hipStreamSynchronize(h->stream));
+    HIP_OK(hipStreamSynchronize(h->stream.s));
     return DVC_OK;
 }
 
@@ -133,8 +98,7 @@ void dvc_quality_destroy(dvc_quality* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    quality_free(h);
+    (void)hipStreamSynchronize(h->stream.s);
     delete h;
 }
 

@@ -112,44 +112,27 @@ hipError_t launch_bgr_to_i420(const uint8_t* src, size_t spitch, size_t sstride,
     return hipGetLastError();
 }
 
-// Layout of a DVC_FMT_I420 / DVC_FMT_NV12 frame (include/dvc.h): luma rows of
-// `pitch`, chroma plane(s) after `crows` luma rows.
-YuvLayout yuv_layout(const uint8_t* base, size_t pitch, int fmt, int crows, size_t fstride)
-{
-    YuvLayout L{};
-    L.base = base;
-    L.ypitch = pitch;
-    L.fstride = fstride;
-    L.uoff = pitch * (size_t)crows;
-    if (fmt == DVC_FMT_NV12) {
-        L.voff = L.uoff + 1;
-        L.cpitch = pitch;
-        L.cstep = 2;
-    } else {
-        L.cpitch = pitch / 2;
-        L.voff = L.uoff + L.cpitch * (size_t)(crows / 2);
-        L.cstep = 1;
-    }
-    return L;
-}
-
-size_t yuv_frame_bytes(size_t pitch, int crows) { return pitch * (size_t)crows * 3 / 2; }
-
 }  // namespace dvc
 
 using dvc_host::fail;
+using dvc_host::FrameFmt;
 
 namespace {
 
-int check_yuv_args(int fmt, int crows, int W, int H, size_t pitch, int n, size_t fstride)
+// The 4:2:0 frames and the BGR frames of one conversion call (host_frames.h)
+int check_yuv_args(int fmt, int crows, int W, int H, size_t pitch, int n, size_t fstride, size_t bgr_pitch,
+                   size_t bgr_stride)
 {
     if (fmt != DVC_FMT_I420 && fmt != DVC_FMT_NV12) return fail(DVC_E_INVALID, "unknown YUV format %d", fmt);
     if (W < 2 || H < 2 || (W & 1) || (H & 1)) return fail(DVC_E_INVALID, "4:2:0 frame %dx%d: sides must be even", W, H);
     const int cr = crows ? crows : H;
     if (cr < H || (cr & 1)) return fail(DVC_E_INVALID, "chroma_rows %d: even and >= height %d", crows, H);
-    if (pitch < (size_t)W || (fmt == DVC_FMT_I420 && (pitch & 1))) return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
+    const FrameFmt yuv{fmt, W, H, cr}, bgr{DVC_FMT_BGR, W, H, 0};
+    if (!pitch_ok(yuv, pitch)) return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
     if (n < 0) return fail(DVC_E_INVALID, "negative frame count");
-    if (n > 1 && fstride < dvc::yuv_frame_bytes(pitch, cr)) return fail(DVC_E_INVALID, "frame stride %zu invalid", fstride);
+    if (n > 1 && fstride < frame_span(yuv, pitch)) return fail(DVC_E_INVALID, "frame stride %zu invalid", fstride);
+    if (!pitch_ok(bgr, bgr_pitch) || (n > 1 && bgr_stride < frame_span(bgr, bgr_pitch)))
+        return fail(DVC_E_INVALID, "BGR pitch %zu / stride %zu invalid", bgr_pitch, bgr_stride);
     return DVC_OK;
 }
 
@@ -216,10 +199,8 @@ int dvc_yuv420_to_bgr(const uint8_t* yuv, size_t pitch, int fmt, int chroma_rows
                       void* hip_stream, uint32_t flags)
 {
     if (!yuv || !bgr) return fail(DVC_E_INVALID, "NULL argument");
-    int rc = check_yuv_args(fmt, chroma_rows, width, height, pitch, n, frame_stride);
+    int rc = check_yuv_args(fmt, chroma_rows, width, height, pitch, n, frame_stride, bgr_pitch, bgr_stride);
     if (rc) return rc;
-    if (bgr_pitch < 3 * (size_t)width || (n > 1 && bgr_stride < bgr_pitch * (height - 1) + 3 * (size_t)width))
-        return fail(DVC_E_INVALID, "BGR pitch %zu / stride %zu invalid", bgr_pitch, bgr_stride);
     if (n == 0) return DVC_OK;
     const int cr = chroma_rows ? chroma_rows : height;
     HIP_OK(hipSetDevice(device));
@@ -257,10 +238,8 @@ int dvc_bgr_to_i420(const uint8_t* bgr, size_t bgr_pitch, size_t bgr_stride, int
                     uint32_t flags)
 {
     if (!yuv || !bgr) return fail(DVC_E_INVALID, "NULL argument");
-    int rc = check_yuv_args(DVC_FMT_I420, chroma_rows, width, height, pitch, n, frame_stride);
+    int rc = check_yuv_args(DVC_FMT_I420, chroma_rows, width, height, pitch, n, frame_stride, bgr_pitch, bgr_stride);
     if (rc) return rc;
-    if (bgr_pitch < 3 * (size_t)width || (n > 1 && bgr_stride < bgr_pitch * (height - 1) + 3 * (size_t)width))
-        return fail(DVC_E_INVALID, "BGR pitch %zu / stride %zu invalid", bgr_pitch, bgr_stride);
     if (n == 0) return DVC_OK;
     const int cr = chroma_rows ? chroma_rows : height;
     HIP_OK(hipSetDevice(device));
