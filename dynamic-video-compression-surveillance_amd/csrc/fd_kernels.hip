@@ -1438,10 +1438,6 @@ __device__ __forceinline__ void store_row(uint8_t* dst, const uint32_t* w, int b
     }
 }
 
-#ifndef DVC_OUT_NTLOAD
-#define DVC_OUT_NTLOAD 0
-#endif
-
 // k_out tile: 64 blocks across (64*B px) x 4 block rows, one wave per block
 // row, one lane per full BxB block, of frame t of the batch. FMT != BGR: the
 // block's pixels from a 4:2:0 surface (B luma bytes per row, the chroma row of
@@ -1464,15 +1460,8 @@ __device__ __forceinline__ void out_tile(const BackArgs& a, int t, int tx, int t
 #pragma unroll
         for (int i = 0; i < B; ++i) {
             const uint32_t* src = reinterpret_cast<const uint32_t*>(f + (size_t)(by + i) * a.pitch + 3 * bx);
-#if DVC_OUT_NTLOAD
-            // the frame's last use (k_front read it a batch earlier): nontemporal
-            // loads leave L2 / MALL to the lines other stages re-read
-#pragma unroll
-            for (int d = 0; d < 3 * B / 4; ++d) px[i][d] = __builtin_nontemporal_load(src + d);
-#else
 #pragma unroll
             for (int d = 0; d < 3 * B / 4; ++d) px[i][d] = src[d];
-#endif
         }
     } else {
 #pragma unroll
@@ -2065,12 +2054,16 @@ hipError_t launch_prime(const uint8_t* bgr, int pitch, uint8_t* gray_tmp, uint32
     return hipGetLastError();
 }
 
-template <int NW>
-static void launch_front_nw(const uint8_t* bgr, int pitch, size_t fstride, const SrcFmt& sf, int n,
-                            const uint8_t* gray_in, uint8_t* gray_out, int gs, uint64_t* mbits, const RowGeom& g,
-                            int ithresh, hipStream_t s, const FrontOut* fo)
+hipError_t launch_front(const uint8_t* bgr, int pitch, size_t fstride, const SrcFmt& sf, int n, const uint8_t* gray_in,
+                        uint8_t* gray_out, int gs, uint64_t* mbits, const RowGeom& g, int ithresh, hipStream_t s,
+                        const FrontOut* fo)
 {
-    constexpr int FT_H = 4 * NW;
+    if (fo && !(fo->B == 4 ? dct4_is_const(fo->M) : fo->B == 8 && dct8_is_const(fo->M)))
+        return hipErrorInvalidValue;   // the fused DCT's constant basis
+    if (fo && fo->B == 8 && sf.fmt != DVC_FMT_BGR) return hipErrorInvalidValue;   // 8x8: BGR frames only
+    if (fo && fo->i420 && (fo->B != 4 || g.W % 4 || g.H % 4)) return hipErrorInvalidValue;   // I420: 4x4, whole blocks
+    // waves per workgroup = tile height / 4 (8 and 16 measured no better; the fused outputs need 4)
+    constexpr int NW = 4, FT_H = 4 * NW;
     const int tx = (g.W + FT_W - 1) / FT_W, ty = (g.H + FT_H - 1) / FT_H;
     // chunks of the batch: ~5120 waves in flight (1280 workgroups of 4 waves),
     // at least 8 frames per chunk — each extra chunk re-reads a warm-up frame
@@ -2099,87 +2092,32 @@ static void launch_front_nw(const uint8_t* bgr, int pitch, size_t fstride, const
     // not the plain one's; DVC_FRONT_XCD overrides
     static const int xcd_env = [] { const char* e = dvc::tune_env("DVC_FRONT_XCD"); return e ? atoi(e) : -1; }();
     const int xcd = xcd_env >= 0 ? xcd_env : (fo ? 1 : 0);
-    // frames in flight per workgroup: the fused BGR front 2 (+1 % against 1 at
-    // 4 workgroups a CU, 119 VGPRs), the others 1; DVC_FRONT_PF overrides
-    static const int pf_env = [] { const char* e = dvc::tune_env("DVC_FRONT_PF"); return e ? atoi(e) : 0; }();
-    const int pf = pf_env > 0 ? pf_env : (fo ? 2 : 1);
-    const dim3 grid(tx, ty, chunks), block(64 * NW);
+    // DVC_FRONT_LDS=<bytes> (experiment): unused dynamic LDS per workgroup, to
+    // cap the fused front's workgroups per CU and leave room to the others
+    static const size_t pad = [] { const char* e = dvc::tune_env("DVC_FRONT_LDS"); return e ? (size_t)atol(e) : 0; }();
     const FrontOut none{};
-    if constexpr (NW == 4 || NW == 8) {
-        if (fo) {
-            // DVC_FRONT_LDS=<bytes> (experiment): unused dynamic LDS per workgroup, to
-            // cap the fused front's workgroups per CU and leave room to the others
-            static const size_t pad = [] { const char* e = dvc::tune_env("DVC_FRONT_LDS"); return e ? (size_t)atol(e) : 0; }();
-            if constexpr (NW == 4) {
-                if (fo->B == 8) {   // 8x8 blocks (BGR frames; launch_front checked the rest)
-                    klaunch((k_front<4, 1, DVC_FMT_BGR, true, 8>), grid, block, pad, s, bgr, pitch, fstride, sf,
-                                       n, chunk, gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, *fo);
-                    return;
-                }
-            }
-            if constexpr (NW == 4) {
-                if (fo->i420) {   // I420 outputs (launch_front: B = 4, NW = 4)
-                    if (sf.fmt == DVC_FMT_NV12)
-                        klaunch((k_front<4, 1, DVC_FMT_NV12, true, 4, true>), grid, block, pad, s, bgr, pitch,
-                                           fstride, sf, n, chunk, gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh,
-                                           xcd, *fo);
-                    else if (sf.fmt == DVC_FMT_I420)
-                        klaunch((k_front<4, 1, DVC_FMT_I420, true, 4, true>), grid, block, pad, s, bgr, pitch,
-                                           fstride, sf, n, chunk, gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh,
-                                           xcd, *fo);
-                    else if (pf == 2)
-                        klaunch((k_front<4, 2, DVC_FMT_BGR, true, 4, true>), grid, block, pad, s, bgr, pitch,
-                                           fstride, sf, n, chunk, gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh,
-                                           xcd, *fo);
-                    else
-                        klaunch((k_front<4, 1, DVC_FMT_BGR, true, 4, true>), grid, block, pad, s, bgr, pitch,
-                                           fstride, sf, n, chunk, gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh,
-                                           xcd, *fo);
-                    return;
-                }
-            }
-            if (sf.fmt == DVC_FMT_NV12)
-                klaunch((k_front<NW, 1, DVC_FMT_NV12, true>), grid, block, pad, s, bgr, pitch, fstride, sf, n,
-                                   chunk, gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, *fo);
-            else if (sf.fmt == DVC_FMT_I420)
-                klaunch((k_front<NW, 1, DVC_FMT_I420, true>), grid, block, pad, s, bgr, pitch, fstride, sf, n,
-                                   chunk, gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, *fo);
-            else if (pf == 2 && NW == 4)
-                klaunch((k_front<4, 2, DVC_FMT_BGR, true>), grid, block, pad, s, bgr, pitch, fstride, sf, n,
-                                   chunk, gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, *fo);
-            else
-                klaunch((k_front<NW, 1, DVC_FMT_BGR, true>), grid, block, pad, s, bgr, pitch, fstride, sf, n,
-                                   chunk, gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, *fo);
-            return;
-        }
+    // one launch: every k_front instantiation takes the same 14 arguments
+    auto go = [&](auto k) {
+        klaunch(k, dim3(tx, ty, chunks), dim3(64 * NW), fo ? pad : 0, s, bgr, pitch, fstride, sf, n, chunk, gray_in,
+                gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, fo ? *fo : none);
+    };
+    // frames in flight per workgroup (PF): the fused BGR front 2 (+1 % against 1
+    // at 4 workgroups a CU, 119 VGPRs), the others 1; the 8x8 blocks 1
+    if (!fo) {
+        if (sf.fmt == DVC_FMT_I420) go(k_front<4, 1, DVC_FMT_I420, false>);
+        else if (sf.fmt == DVC_FMT_NV12) go(k_front<4, 1, DVC_FMT_NV12, false>);
+        else go(k_front<4, 1, DVC_FMT_BGR, false>);
+    } else if (fo->B == 8) {   // 8x8 blocks (BGR frames, checked above)
+        go(k_front<4, 1, DVC_FMT_BGR, true, 8>);
+    } else if (fo->i420) {   // I420 outputs (4x4 blocks, checked above)
+        if (sf.fmt == DVC_FMT_NV12) go(k_front<4, 1, DVC_FMT_NV12, true, 4, true>);
+        else if (sf.fmt == DVC_FMT_I420) go(k_front<4, 1, DVC_FMT_I420, true, 4, true>);
+        else go(k_front<4, 2, DVC_FMT_BGR, true, 4, true>);
+    } else {
+        if (sf.fmt == DVC_FMT_NV12) go(k_front<4, 1, DVC_FMT_NV12, true>);
+        else if (sf.fmt == DVC_FMT_I420) go(k_front<4, 1, DVC_FMT_I420, true>);
+        else go(k_front<4, 2, DVC_FMT_BGR, true>);
     }
-    if (sf.fmt == DVC_FMT_I420)
-        klaunch((k_front<NW, 1, DVC_FMT_I420, false>), grid, block, 0, s, bgr, pitch, fstride, sf, n, chunk,
-                           gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, none);
-    else if (sf.fmt == DVC_FMT_NV12)
-        klaunch((k_front<NW, 1, DVC_FMT_NV12, false>), grid, block, 0, s, bgr, pitch, fstride, sf, n, chunk,
-                           gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, none);
-    else if (pf == 2)
-        klaunch((k_front<NW, 2, DVC_FMT_BGR, false>), grid, block, 0, s, bgr, pitch, fstride, sf, n, chunk,
-                           gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, none);
-    else
-        klaunch((k_front<NW, 1, DVC_FMT_BGR, false>), grid, block, 0, s, bgr, pitch, fstride, sf, n, chunk,
-                           gray_in, gray_out, gs, mbits, g.W, g.H, g.WW, ithresh, xcd, none);
-}
-
-hipError_t launch_front(const uint8_t* bgr, int pitch, size_t fstride, const SrcFmt& sf, int n, const uint8_t* gray_in,
-                        uint8_t* gray_out, int gs, uint64_t* mbits, const RowGeom& g, int ithresh, hipStream_t s,
-                        const FrontOut* fo)
-{
-    if (fo && !(fo->B == 4 ? dct4_is_const(fo->M) : fo->B == 8 && dct8_is_const(fo->M)))
-        return hipErrorInvalidValue;   // the fused DCT's constant basis
-    if (fo && fo->B == 8 && sf.fmt != DVC_FMT_BGR) return hipErrorInvalidValue;   // 8x8: BGR frames only
-    if (fo && fo->i420 && (fo->B != 4 || g.W % 4 || g.H % 4)) return hipErrorInvalidValue;   // I420: 4x4, whole blocks
-    // waves per workgroup = tile height / 4 (DVC_FRONT_NW: 4, 8 or 16; the fused outputs need 4)
-    static const int nw = [] { const char* e = dvc::tune_env("DVC_FRONT_NW"); return e ? atoi(e) : 4; }();
-    if (nw == 16 && !fo) launch_front_nw<16>(bgr, pitch, fstride, sf, n, gray_in, gray_out, gs, mbits, g, ithresh, s, nullptr);
-    else if (nw == 8 && !(fo && (fo->B == 8 || fo->i420))) launch_front_nw<8>(bgr, pitch, fstride, sf, n, gray_in, gray_out, gs, mbits, g, ithresh, s, fo);
-    else launch_front_nw<4>(bgr, pitch, fstride, sf, n, gray_in, gray_out, gs, mbits, g, ithresh, s, fo);
     return hipGetLastError();
 }
 

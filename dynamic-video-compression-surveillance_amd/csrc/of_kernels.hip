@@ -50,20 +50,13 @@ namespace dvc {
 // the address rate (TA), not the bytes, bounds the M gathers.
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
-#if defined(DVC_S2_EXP) && DVC_S2_EXP == 4   // (timing experiment, wrong results) 16-B aligned R loads
-#define DVC_ALIGN_R(p) reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(p) & ~(uintptr_t)15)
-#else
-#define DVC_ALIGN_R(p) (p)
-#endif
 __device__ __forceinline__ void ld5(const float* p, float* o)
 {
-    p = DVC_ALIGN_R(p);
     const f4u a = *reinterpret_cast<const f4u*>(p);
     o[0] = a.x, o[1] = a.y, o[2] = a.z, o[3] = a.w, o[4] = p[4];
 }
 __device__ __forceinline__ void ld10(const float* p, float* o)
 {
-    p = DVC_ALIGN_R(p);
     const f4u a = *reinterpret_cast<const f4u*>(p), b = *reinterpret_cast<const f4u*>(p + 4);
     const f2u c = *reinterpret_cast<const f2u*>(p + 8);
     o[0] = a.x, o[1] = a.y, o[2] = a.z, o[3] = a.w, o[4] = b.x, o[5] = b.y, o[6] = b.z, o[7] = b.w, o[8] = c.x,
@@ -79,9 +72,6 @@ __device__ __forceinline__ float border_w(int d) { return d < 2 ? 0.14f : 0.4472
 namespace {
 
 constexpr int PT_W = 64, PT_H = 16;   // poly-expansion tile (level pixels)
-#ifndef DVC_POLY_FMA
-#define DVC_POLY_FMA 1
-#endif
 constexpr int FL_W = 32, FL_H = 16;   // flow tile (32 wide: <= 26 KB LDS, 6 workgroups per CU)
 
 // Ring slot of frame number a. The launchers pass frame numbers through
@@ -180,16 +170,11 @@ __device__ __forceinline__ void poly_tile(const float* sI, float* sv, const Poly
             const float* M = INT ? c - 3 * k : sv + (i * SV + (max(x - k, 0) - (x0 - PN))) * 3;
             const float gk = pc.g[PN + k], xgk = pc.xg[PN + k];
             const double tg = (double)(P[0] + M[0]);
-#if DVC_POLY_FMA
             // tg and the taps are floats: their double product has <= 48
             // significant bits, so it is exact and fma(tg, g, b) rounds exactly
             // as b + tg * g (one v_fma_f64 instead of v_mul_f64 + v_add_f64)
             b1 = __builtin_fma(tg, (double)gk, b1);
             b4 = __builtin_fma(tg, (double)pc.xxg[PN + k], b4);
-#else
-            b1 += tg * (double)gk;
-            b4 += tg * (double)pc.xxg[PN + k];
-#endif
             b2 += (double)((P[0] - M[0]) * xgk);
             b3 += (double)((P[1] + M[1]) * gk);
             b6 += (double)((P[1] - M[1]) * xgk);
@@ -1055,14 +1040,8 @@ __device__ unsigned long long g_scan_stamps[32 * 96 * 8];
 #ifndef DVC_SCAN_UF
 #define DVC_SCAN_UF 8   // columns per register set of the horizontal chains
 #endif
-#ifndef DVC_SCAN_PRIO
-#define DVC_SCAN_PRIO 0
-#endif
 #ifndef DVC_SCAN_FG
 #define DVC_SCAN_FG 2   // rows per group of the fast vertical sums' ring loads
-#endif
-#ifndef DVC_SCAN_ILV
-#define DVC_SCAN_ILV 1   // interleave the M gathers with the vertical sums (interior blocks)
 #endif
 #ifndef DVC_SCAN_VG
 #define DVC_SCAN_VG 1   // rows per group of the generic vertical sums' ring loads
@@ -1211,9 +1190,6 @@ __device__ void scan_strip(const ScanArgs& S, int t, int s, float* sM, double* s
     //     b+1's M into the ring (FarnebackUpdateMatrices); phase 3 solves b.
     const int slot_last = (h - 1) % RING;
     if (tid < 64) {
-        // wave 0 carries the strip's critical path (the wavefront hand-off and
-        // the serial chains): issue priority over the M waves sharing its SIMD
-        if (DVC_SCAN_PRIO) __builtin_amdgcn_s_setprio(DVC_SCAN_PRIO);
         for (int y0 = 0; y0 < h; y0 += RB) {
             const int yb = y0 / RB, nrow = min(RB, h - y0);
             STAMP(0);
@@ -1290,7 +1266,6 @@ __device__ void scan_strip(const ScanArgs& S, int t, int s, float* sM, double* s
             STAMP(5);
             if (!alive) break;   // an aborted launch drains
         }
-        if (DVC_SCAN_PRIO) __builtin_amdgcn_s_setprio(0);
         return;
     }
     // M waves. The pipelined blocks' M positions: P = block b+1 (its R loads in
@@ -1337,7 +1312,7 @@ __device__ void scan_strip(const ScanArgs& S, int t, int s, float* sM, double* s
         STAMP(0);
         // phase 1: vertical recurrence for the block's rows: vsum += (float)(M[y+m] - M[y-m-1])
         const bool fast = m == MM && y0 - m - 1 >= 0 && y0 + RB - 1 + m <= h - 1;   // uniform
-        if (KV == 1 && fast && DVC_SCAN_ILV) {
+        if (KV == 1 && fast) {
             // every thread runs a chain (threads past the last one repeat it:
             // same values to the same sV words), so the block is straight-line
             const int chc = min(mt, nch - 1), jc = chc / 5, cc = chc - 5 * jc;
@@ -1500,9 +1475,6 @@ __global__ void __launch_bounds__(NT, OCC) k_flow_scan(ScanArgs S)
 // ring of k_flow_scan is gone. Sum buffers are laid out [row][channel][column]
 // (74 doubles a line: conflict-free 16-B chain reads and writes), so the chain
 // reads its operands as b128 pairs and issues ~2 instructions a column.
-#ifndef DVC_S2_EXP
-#define DVC_S2_EXP 0   // timing experiments of variant builds only (tools/build_variant.sh -DDVC_S2_EXP=k)
-#endif
 namespace scan2 {
 constexpr int SW = 64, RB = 12, M = 4, HW = 2 * M + 1, NC = SW + HW;
 constexpr int NT = 1024, NMT = NT - 64;
@@ -1697,7 +1669,7 @@ __device__ __forceinline__ void scan2_role(const ScanArgs& S, double* sv0, float
 #pragma unroll
                         for (int pp = 0; pp < 13; ++pp) win[pp] = v2[pp];
 #pragma unroll
-                        for (int gi = 0; gi < (DVC_S2_EXP == 7 ? 0 : SW / 8); ++gi) {
+                        for (int gi = 0; gi < SW / 8; ++gi) {
                             d2 nxt[4];
                             if (13 + 4 * gi + 3 < NPAIR) {
 #pragma unroll
@@ -1786,13 +1758,7 @@ __device__ __forceinline__ void scan2_role(const ScanArgs& S, double* sv0, float
                 float fx, fy;
                 (void)mat_corner(Q.xs[0], Q.ys[0], Q.dx[0], Q.dy[0], w, h, x1, y1, fx, fy);
                 const int x1c = min(max(x1, 0), max(w - 2, 0)), y1c = min(max(y1, 0), max(h - 2, 0));
-#if DVC_S2_EXP == 1   // (timing experiment, wrong results) undisplaced R1 reads
-                ld10(R1 + 5u * (uint32_t)(min(Q.ys[0] + row, h - 1) * w + min(Q.xs[0], w - 2)), Q.pq[0] + 10 * row);
-#elif DVC_S2_EXP == 2   // (timing experiment, wrong results) no R1 reads
-                for (int u = 0; u < 10; ++u) Q.pq[0][10 * row + u] = Q.r0[0][u % 5];
-#else
                 ld10(R1 + 5u * (uint32_t)((y1c + row) * w + x1c), Q.pq[0] + 10 * row);
-#endif
             };
             {   // p0: M rows 0 .. RB + M - 1 (clamped) -> transfer buffer 0, two passes
                 flowld(PB, 1);
@@ -1827,7 +1793,7 @@ __device__ __forceinline__ void scan2_role(const ScanArgs& S, double* sv0, float
                 // interval's gathers: vmcnt counts loads and stores in one queue,
                 // so a store issued before a load makes the next wait for that
                 // load wait for the store's completion too
-                const bool sdo = k >= 1 && sslot >= 0 && DVC_S2_EXP != 6;
+                const bool sdo = k >= 1 && sslot >= 0;
                 float fx[SPX], fy[SPX];
                 if (sdo) {
                     const int b = k - 1;
@@ -1837,11 +1803,7 @@ __device__ __forceinline__ void scan2_role(const ScanArgs& S, double* sv0, float
                         const double* gg = sv0 + (size_t)(b % 3) * SVB + (i0 + q) * 5 * P + xl;
                         const double g11 = gg[0] * g.box_scale, g12 = gg[P] * g.box_scale, g22 = gg[2 * P] * g.box_scale;
                         const double h1 = gg[3 * P] * g.box_scale, h2 = gg[4 * P] * g.box_scale;
-#if DVC_S2_EXP == 5   // (timing experiment, wrong results) no division in the solve
-                        const double idet = (g11 * g22 - g12 * g12 + 1e-3) * 0.5;
-#else
                         const double idet = 1. / (g11 * g22 - g12 * g12 + 1e-3);
-#endif
                         fx[q] = (float)((g11 * h2 - g12 * h1) * idet);
                         fy[q] = (float)((g22 * h1 - g12 * h2) * idet);
                     }
@@ -1876,11 +1838,11 @@ __device__ __forceinline__ void scan2_role(const ScanArgs& S, double* sv0, float
                 const int vb = k + 1;
                 const float* t0 = tb0 + (size_t)(vb & 1) * TB + vj * 5 + vc;
                 double* svb = sv0 + (size_t)(vb % 3) * SVB + vc * P + vj;
-                if (DVC_S2_EXP != 3 && vth && vb < NB) scan2_vpart<0, RB / 2>(vb, t0, svb, hist, vsum);
+                if (vth && vb < NB) scan2_vpart<0, RB / 2>(vb, t0, svb, hist, vsum);
                 __builtin_amdgcn_sched_barrier(0);
                 ldR1(Y, 1);
                 __builtin_amdgcn_sched_barrier(0);
-                if (DVC_S2_EXP != 3 && vth && vb < NB) scan2_vpart<RB / 2, RB>(vb, t0, svb, hist, vsum);
+                if (vth && vb < NB) scan2_vpart<RB / 2, RB>(vb, t0, svb, hist, vsum);
                 flowld(X, k + 4);
                 __builtin_amdgcn_sched_barrier(0);
                 solve_store();
@@ -2616,23 +2578,10 @@ __global__ void __launch_bounds__(256) k_flow_up(FlowArgs A, float* __restrict__
     }
 }
 
-// k_flow_scan variants for box radius m <= 4 (winsize <= 9, the reference's):
-// strips of 64 columns x blocks of RB rows, NT threads (the table below, the
-// launch switch in of_launch_flow); DVC_OF_SCAN=<index> picks one for A/B runs
-namespace {
-struct ScanCfg { int nt, rb; };
-constexpr ScanCfg kScanCfg4[] = {{512, 12}, {512, 6}, {256, 6}, {384, 6}, {256, 8}, {512, 8}};
-int scan_cfg_index()
-{
-    static const int v = [] {
-        const char* e = dvc::tune_env("DVC_OF_SCAN");
-        const int k = e ? atoi(e) : 0;
-        return k >= 0 && k < (int)(sizeof(kScanCfg4) / sizeof(kScanCfg4[0])) ? k : 0;
-    }();
-    return v;
-}
-int scan_rb(const OfGeom& g) { return g.m <= 4 ? kScanCfg4[scan_cfg_index()].rb : 8; }
-}  // namespace
+// k_flow_scan's blocks of rows: 12 for box radius m <= 4 (winsize <= 9, the
+// reference's), 8 above; strips of 64 columns, 512 threads (the launch switch
+// in of_launch_flow)
+static int scan_rb(const OfGeom& g) { return g.m <= 4 ? 12 : 8; }
 
 size_t of_scan_slots(const OfGeom& g, int w, int h)
 {
@@ -2685,7 +2634,6 @@ hipError_t of_launch_flow(const OfGeom& g, const Level* lv, const OfBufs& b, lon
             A.mring = b.mring;
             A.dbg_flow = b.dbg_flow;
             if (g.sliding) {   // OpenCV's running box sums: strip wavefront
-                const int scan_cfg = scan_cfg_index();
                 const int sw = 64, rb = scan_rb(g);
                 ScanArgs S{};
                 S.f = A;
@@ -2726,27 +2674,14 @@ hipError_t of_launch_flow(const OfGeom& g, const Level* lv, const OfBufs& b, lon
                 const size_t lds_b = scan_lds_bytes(sw, rb, g.m);
                 const int per_cu = std::max(1, std::min(8, (int)(160 * 1024 / lds_b)));
                 const int items = S.S * n, grid_s = std::max(1, std::min(items, per_cu * cus));
-                const int sm2 = S.f.src_mode == 2;
-                const int sel = g.m <= 4 ? 2 + 2 * scan_cfg + sm2 : sm2;
-                switch (sel) {
-#define DVC_SCAN_CASE(i, NTv, RBv, SM, MMv, OCCv) \
-    case i: hipLaunchKernelGGL((k_flow_scan<64, RBv, NTv, SM, MMv, OCCv>), dim3(grid_s), dim3(NTv), lds_b, s, S); break;
-                    DVC_SCAN_CASE(0, 512, 8, 0, OF_MAX_BOX_M, 2)
-                    DVC_SCAN_CASE(1, 512, 8, 2, OF_MAX_BOX_M, 2)
-                    DVC_SCAN_CASE(2, 512, 12, 0, 4, 4)
-                    DVC_SCAN_CASE(3, 512, 12, 2, 4, 4)
-                    DVC_SCAN_CASE(4, 512, 6, 0, 4, 6)
-                    DVC_SCAN_CASE(5, 512, 6, 2, 4, 6)
-                    DVC_SCAN_CASE(6, 256, 6, 0, 4, 4)
-                    DVC_SCAN_CASE(7, 256, 6, 2, 4, 4)
-                    DVC_SCAN_CASE(8, 384, 6, 0, 4, 6)
-                    DVC_SCAN_CASE(9, 384, 6, 2, 4, 6)
-                    DVC_SCAN_CASE(10, 256, 8, 0, 4, 4)
-                    DVC_SCAN_CASE(11, 256, 8, 2, 4, 4)
-                    DVC_SCAN_CASE(12, 512, 8, 0, 4, 6)
-                    DVC_SCAN_CASE(13, 512, 8, 2, 4, 6)
-#undef DVC_SCAN_CASE
-                }
+                const bool sm2 = S.f.src_mode == 2;
+#define DVC_SCAN_LAUNCH(RBv, SM, MMv, OCCv) \
+    hipLaunchKernelGGL((k_flow_scan<64, RBv, 512, SM, MMv, OCCv>), dim3(grid_s), dim3(512), lds_b, s, S)
+                if (g.m > 4 && sm2) DVC_SCAN_LAUNCH(8, 2, OF_MAX_BOX_M, 2);
+                else if (g.m > 4) DVC_SCAN_LAUNCH(8, 0, OF_MAX_BOX_M, 2);
+                else if (sm2) DVC_SCAN_LAUNCH(12, 2, 4, 4);
+                else DVC_SCAN_LAUNCH(12, 0, 4, 4);
+#undef DVC_SCAN_LAUNCH
             } else if (g.m == 4) {
                 if (kernel && k == k_lo) *kernel = DVC_KTIME_FLOW;
                 hipLaunchKernelGGL(k_flow<4>, grid, dim3(256), lds, s, A);

@@ -56,6 +56,44 @@ def test_shipping_library_reads_no_tuning_knobs():
     assert all(n in allowed or n.startswith((b"DVC_FLAG_", b"DVC_FMT_")) for n in names), names
 
 
+def test_shipping_library_holds_exactly_the_launchable_variants():
+    """The two variant families hold the instantiations their launch code can
+    select and no other (launch_front in fd_kernels.hip, of_launch_flow in
+    of_kernels.hip): a new variant arrives together with its launch path. Read
+    from the mangled kernel names in the library's (uncompressed) code object."""
+    import dvc_amd
+    blob = open(dvc_amd._native.build(), "rb").read()
+
+    def variants(name):
+        found = set(re.findall(rb"_ZN3dvc%d%sI((?:L[ib]\d+E)+)E" % (len(name), name), blob))
+        return {tuple(int(v) for v in re.findall(rb"L[ib](\d+)E", f)) for f in found}
+
+    BGR, I420, NV12 = 0, 1, 2   # DVC_FMT_*
+    # k_front<NW, PF, FMT, OUT, OB, OI>: waves, frames in flight, input format,
+    # fused outputs, their block size, I420 output surfaces
+    assert variants(b"k_front") == {
+        (4, 1, BGR, 0, 4, 0),    # plain front, BGR frames
+        (4, 1, I420, 0, 4, 0),   # plain front, I420 frames
+        (4, 1, NV12, 0, 4, 0),   # plain front, NV12 frames
+        (4, 2, BGR, 1, 4, 0),    # fused 4x4, BGR frames, two frames in flight
+        (4, 1, I420, 1, 4, 0),   # fused 4x4, I420 frames
+        (4, 1, NV12, 1, 4, 0),   # fused 4x4, NV12 frames
+        (4, 2, BGR, 1, 4, 1),    # fused 4x4 with I420 outputs, BGR frames
+        (4, 1, I420, 1, 4, 1),   # fused 4x4 with I420 outputs, I420 frames
+        (4, 1, NV12, 1, 4, 1),   # fused 4x4 with I420 outputs, NV12 frames
+        (4, 1, BGR, 1, 8, 0),    # fused 8x8, BGR frames
+    }
+    # k_flow_scan<SW, RB, NT, SM, MM, OCC>: strip width, rows a block, threads,
+    # source mode (0 = no prior flow, 2 = a flow buffer), largest box radius,
+    # occupancy bound
+    assert variants(b"k_flow_scan") == {
+        (64, 8, 512, 0, 8, 2),    # box radius 5 .. 8 (winsize 10 .. 17), first iteration of the top level
+        (64, 8, 512, 2, 8, 2),    # box radius 5 .. 8, every other iteration
+        (64, 12, 512, 0, 4, 4),   # box radius <= 4 (winsize <= 9), first iteration of the top level
+        (64, 12, 512, 2, 4, 4),   # box radius <= 4, every other iteration
+    }
+
+
 def test_abi_gaussian_taps_host_only():
     """dvc_gaussian_taps_q8 is pure host code: same taps as the oracle."""
     import dvc_amd
