@@ -38,21 +38,6 @@ FORMATS = {"BGR": FMT_BGR, "I420": FMT_I420, "NV12": FMT_NV12}
 PLANE_GRAY, PLANE_MOTION, PLANE_FILTERED, PLANE_ACC, PLANE_DILATED = range(5)
 OF_PLANE_RAW, OF_PLANE_SMOOTH, OF_PLANE_MORPH, OF_PLANE_RECT, OF_PLANE_GRAY = range(5)
 
-# every symbol include/dvc.h declares (checked by tests/test_host.py::test_abi_exports_every_declared_symbol)
-EXPORTS = [
-    "dvc_abi_version", "dvc_last_error", "dvc_device_count", "dvc_fd_create", "dvc_fd_prime",
-    "dvc_fd_step", "dvc_fd_sync", "dvc_fd_get_stats", "dvc_fd_read_plane", "dvc_fd_ktime",
-    "dvc_fd_destroy", "dvc_gaussian_taps_q8", "dvc_contour_filter", "dvc_fd_step_batch",
-    "dvc_of_create", "dvc_of_prime", "dvc_of_step", "dvc_of_step_batch", "dvc_of_sync", "dvc_of_get_stats",
-    "dvc_of_read_plane", "dvc_of_read_flow", "dvc_of_ktime", "dvc_of_destroy", "dvc_of_compress",
-    "dvc_of_debug_read", "dvc_host_alloc", "dvc_host_free", "dvc_yuv420_to_bgr", "dvc_bgr_to_i420",
-    "dvc_copy_rate", "dvc_ofc_create", "dvc_ofc_run", "dvc_ofc_sync", "dvc_ofc_destroy",
-    "dvc_fd_set_state", "dvc_of_set_state", "dvc_fd_ktime_kernel", "dvc_of_ktime_kernel",
-    "dvc_fd_graph_stats", "dvc_jpeg_create", "dvc_jpeg_destroy", "dvc_jpeg_header", "dvc_jpeg_bound",
-    "dvc_jpeg_encode", "dvc_jpeg_sync", "dvc_jpegd_create", "dvc_jpegd_destroy", "dvc_jpegd_set_header",
-    "dvc_jpegd_decode", "dvc_jpegd_sync", "dvc_quality_create", "dvc_quality_compare", "dvc_quality_sync",
-    "dvc_quality_destroy",
-]
 ABI_VERSION = 10
 MAX_BATCH = 512
 
@@ -147,6 +132,81 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
+# The C-ABI: name -> (restype, argtypes), one entry per function include/dvc.h
+# declares, in the header's order. lib() binds exactly this table and
+# tests/test_host.py checks every entry against the header's prototype.
+_I, _Z, _P, _U32, _F, _D = (ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float,
+                            ctypes.c_double)
+_PI, _PZ, _PD, _PU64, _PP = (ctypes.POINTER(t) for t in (_I, _Z, _D, ctypes.c_uint64, _P))
+SIGNATURES = {
+    # standalone conversions
+    "dvc_yuv420_to_bgr": (_I, (_P, _Z, _I, _I, _I, _I, _I, _Z, _P, _Z, _Z, _I, _P, _U32)),
+    "dvc_bgr_to_i420": (_I, (_P, _Z, _Z, _I, _I, _I, _P, _Z, _I, _Z, _I, _P, _U32)),
+    # library / device introspection, page-locked host memory
+    "dvc_abi_version": (_I, ()),
+    "dvc_last_error": (ctypes.c_char_p, ()),
+    "dvc_device_count": (_I, (_PI,)),
+    "dvc_host_alloc": (_I, (_Z, _PP)),
+    "dvc_host_free": (None, (_P,)),
+    # frame-differencing path
+    "dvc_fd_create": (_I, (ctypes.POINTER(FdParams), _I, _P, _PP)),
+    "dvc_fd_prime": (_I, (_P, _P, _Z)),
+    "dvc_fd_set_state": (_I, (_P, _P, _P)),
+    "dvc_fd_step": (_I, (_P, _P, _Z, _P, _P, _P)),
+    "dvc_fd_step_batch": (_I, (_P, _P, _Z, _Z, _I, _P, _P, _Z)),
+    "dvc_fd_sync": (_I, (_P,)),
+    "dvc_fd_get_stats": (_I, (_P, ctypes.POINTER(FdStats))),
+    "dvc_fd_read_plane": (_I, (_P, _I, _P)),
+    "dvc_fd_ktime": (_I, (_P, _PD, _PU64, _I)),
+    "dvc_fd_ktime_kernel": (_I, (_P,)),
+    "dvc_fd_graph_stats": (_I, (_P, _PU64, _PU64)),
+    "dvc_fd_destroy": (None, (_P,)),
+    "dvc_contour_filter": (_I, (_P, _I, _I, ctypes.c_int64, _I, _P, _PU64)),
+    # optical-flow path
+    "dvc_of_create": (_I, (ctypes.POINTER(OfParams), _I, _P, _PP)),
+    "dvc_of_prime": (_I, (_P, _P, _Z)),
+    "dvc_of_set_state": (_I, (_P, _P, _P, _I)),
+    "dvc_of_step": (_I, (_P, _P, _Z, _P, _P)),
+    "dvc_of_step_batch": (_I, (_P, _P, _Z, _Z, _I, _P, _Z, _P, _Z)),
+    "dvc_of_sync": (_I, (_P,)),
+    "dvc_of_get_stats": (_I, (_P, ctypes.POINTER(OfStats))),
+    "dvc_of_read_plane": (_I, (_P, _I, _P)),
+    "dvc_of_read_flow": (_I, (_P, _P)),
+    "dvc_of_ktime": (_I, (_P, _PD, _PU64, _I)),
+    "dvc_of_ktime_kernel": (_I, (_P,)),
+    "dvc_of_destroy": (None, (_P,)),
+    "dvc_of_debug_read": (_I, (_P, _I, _I, _P, _PI, _PI)),
+    "dvc_of_compress": (_I, (_P, _Z, _P, _I, _I, _F, _I, _P)),
+    "dvc_ofc_create": (_I, (_I, _I, _F, _I, _I, _P, _U32, _PP)),
+    "dvc_ofc_run": (_I, (_P, _P, _Z, _Z, _P, _Z, _Z, _I, _I, _P, _Z)),
+    "dvc_ofc_sync": (_I, (_P,)),
+    "dvc_ofc_destroy": (None, (_P,)),
+    # Motion-JPEG encoder and decoder
+    "dvc_jpeg_create": (_I, (_I, _I, _I, _I, _I, _I, _P, _U32, _PP)),
+    "dvc_jpeg_destroy": (None, (_P,)),
+    "dvc_jpeg_header": (_I, (_P, _P, _Z, _PZ)),
+    "dvc_jpeg_bound": (_I, (_I, _I, _I, _PZ)),
+    "dvc_jpeg_encode": (_I, (_P, _P, _Z, _Z, _I, _P, _Z, _P)),
+    "dvc_jpeg_sync": (_I, (_P,)),
+    "dvc_jpegd_create": (_I, (_I, _I, _I, _I, _P, _U32, _PP)),
+    "dvc_jpegd_destroy": (None, (_P,)),
+    "dvc_jpegd_set_header": (_I, (_P, _P, _Z, _PZ, _PI, _PI, _PI)),
+    "dvc_jpegd_decode": (_I, (_P, _P, _Z, _P, _I, _P, _Z, _Z, _P)),
+    "dvc_jpegd_sync": (_I, (_P,)),
+    # quality metrics
+    "dvc_quality_create": (_I, (_I, _I, _I, _I, _P, _U32, _PP)),
+    "dvc_quality_compare": (_I, (_P, _P, _Z, _Z, _P, _Z, _Z, _I, _P)),
+    "dvc_quality_sync": (_I, (_P,)),
+    "dvc_quality_destroy": (None, (_P,)),
+    # parity helpers and diagnostics
+    "dvc_gaussian_taps_q8": (_I, (_I, _D, ctypes.POINTER(ctypes.c_uint16))),
+    "dvc_copy_rate": (_I, (_I, _Z, _I, _I, _PD)),
+}
+EXPORTS = list(SIGNATURES)
+# An older build loaded for an A/B run (DVC_LIB_PATH with DVC_ALLOW_ABI_MISMATCH=1)
+# may lack these; FDWorker.ktime_kernel and OFWorker.ktime_kernel fall back.
+OPTIONAL = ("dvc_fd_ktime_kernel", "dvc_fd_graph_stats", "dvc_of_ktime_kernel")
+
 _lib = None
 
 
@@ -169,116 +229,7 @@ def lib() -> ctypes.CDLL:
     except Exception:
         pass
     L = ctypes.CDLL(path)
-    vp, u8p = ctypes.c_void_p, ctypes.c_void_p
-    L.dvc_abi_version.restype = ctypes.c_int
-    L.dvc_last_error.restype = ctypes.c_char_p
-    L.dvc_device_count.argtypes = [ctypes.POINTER(ctypes.c_int)]
-    L.dvc_fd_create.argtypes = [ctypes.POINTER(FdParams), ctypes.c_int, vp, ctypes.POINTER(vp)]
-    L.dvc_fd_prime.argtypes = [vp, u8p, ctypes.c_size_t]
-    L.dvc_fd_set_state.argtypes = [vp, u8p, u8p]
-    L.dvc_fd_set_state.restype = ctypes.c_int
-    L.dvc_of_set_state.argtypes = [vp, u8p, u8p, ctypes.c_int]
-    L.dvc_of_set_state.restype = ctypes.c_int
-    L.dvc_fd_step.argtypes = [vp, u8p, ctypes.c_size_t, u8p, u8p, u8p]
-    L.dvc_fd_sync.argtypes = [vp]
-    L.dvc_fd_get_stats.argtypes = [vp, ctypes.POINTER(FdStats)]
-    L.dvc_fd_read_plane.argtypes = [vp, ctypes.c_int, u8p]
-    L.dvc_fd_ktime.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
-    if hasattr(L, "dvc_fd_ktime_kernel"):   # (an older build under DVC_LIB_PATH lacks it)
-        L.dvc_fd_ktime_kernel.argtypes = [vp]
-        L.dvc_fd_ktime_kernel.restype = ctypes.c_int
-    if hasattr(L, "dvc_fd_graph_stats"):
-        L.dvc_fd_graph_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-        L.dvc_fd_graph_stats.restype = ctypes.c_int
-    if hasattr(L, "dvc_of_ktime_kernel"):
-        L.dvc_of_ktime_kernel.argtypes = [vp]
-        L.dvc_of_ktime_kernel.restype = ctypes.c_int
-    L.dvc_fd_destroy.argtypes = [vp]
-    L.dvc_fd_destroy.restype = None
-    L.dvc_gaussian_taps_q8.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_uint16)]
-    L.dvc_fd_step_batch.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, u8p, u8p,
-                                    ctypes.c_size_t]
-    L.dvc_contour_filter.argtypes = [u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, u8p,
-                                     ctypes.POINTER(ctypes.c_uint64)]
-    L.dvc_of_create.argtypes = [ctypes.POINTER(OfParams), ctypes.c_int, vp, ctypes.POINTER(vp)]
-    L.dvc_of_prime.argtypes = [vp, u8p, ctypes.c_size_t]
-    L.dvc_of_step.argtypes = [vp, u8p, ctypes.c_size_t, u8p, u8p]
-    L.dvc_of_step_batch.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t,
-                                    u8p, ctypes.c_size_t]
-    L.dvc_of_sync.argtypes = [vp]
-    L.dvc_of_get_stats.argtypes = [vp, ctypes.POINTER(OfStats)]
-    L.dvc_of_read_plane.argtypes = [vp, ctypes.c_int, u8p]
-    L.dvc_of_read_flow.argtypes = [vp, vp]
-    L.dvc_of_ktime.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
-    L.dvc_of_destroy.argtypes = [vp]
-    L.dvc_of_debug_read.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_int),
-                                    ctypes.POINTER(ctypes.c_int)]
-    L.dvc_of_debug_read.restype = ctypes.c_int
-    L.dvc_of_destroy.restype = None
-    L.dvc_of_compress.argtypes = [u8p, ctypes.c_size_t, u8p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
-                                  u8p]
-    L.dvc_ofc_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int, vp,
-                                 ctypes.c_uint32, ctypes.POINTER(vp)]
-    L.dvc_ofc_run.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_size_t,
-                              ctypes.c_int, ctypes.c_int, u8p, ctypes.c_size_t]
-    L.dvc_ofc_sync.argtypes = [vp]
-    L.dvc_ofc_destroy.argtypes = [vp]
-    L.dvc_ofc_destroy.restype = None
-    for name in ("dvc_ofc_create", "dvc_ofc_run", "dvc_ofc_sync"):
-        getattr(L, name).restype = ctypes.c_int
-    L.dvc_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(vp)]
-    L.dvc_host_alloc.restype = ctypes.c_int
-    L.dvc_host_free.argtypes = [vp]
-    L.dvc_host_free.restype = None
-    L.dvc_yuv420_to_bgr.argtypes = [u8p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                    ctypes.c_int, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
-                                    vp, ctypes.c_uint32]
-    L.dvc_bgr_to_i420.argtypes = [u8p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                  u8p, ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, vp,
-                                  ctypes.c_uint32]
-    L.dvc_copy_rate.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
-                                ctypes.POINTER(ctypes.c_double)]
-    L.dvc_copy_rate.restype = ctypes.c_int
-    L.dvc_yuv420_to_bgr.restype = ctypes.c_int
-    L.dvc_jpeg_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                  vp, ctypes.c_uint32, ctypes.POINTER(vp)]
-    L.dvc_jpeg_destroy.argtypes = [vp]
-    L.dvc_jpeg_destroy.restype = None
-    L.dvc_jpeg_header.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-    L.dvc_jpeg_bound.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
-    L.dvc_jpeg_encode.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_size_t, vp]
-    L.dvc_jpeg_sync.argtypes = [vp]
-    for name in ("dvc_jpeg_create", "dvc_jpeg_header", "dvc_jpeg_bound", "dvc_jpeg_encode", "dvc_jpeg_sync"):
-        getattr(L, name).restype = ctypes.c_int
-    L.dvc_jpegd_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint32,
-                                   ctypes.POINTER(vp)]
-    L.dvc_jpegd_destroy.argtypes = [vp]
-    L.dvc_jpegd_destroy.restype = None
-    L.dvc_jpegd_set_header.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
-                                       ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
-                                       ctypes.POINTER(ctypes.c_int)]
-    L.dvc_jpegd_decode.argtypes = [vp, u8p, ctypes.c_size_t, vp, ctypes.c_int, u8p, ctypes.c_size_t, ctypes.c_size_t, vp]
-    L.dvc_jpegd_sync.argtypes = [vp]
-    for name in ("dvc_jpegd_create", "dvc_jpegd_set_header", "dvc_jpegd_decode", "dvc_jpegd_sync"):
-        getattr(L, name).restype = ctypes.c_int
-    L.dvc_quality_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_uint32,
-                                     ctypes.POINTER(vp)]
-    L.dvc_quality_compare.argtypes = [vp, u8p, ctypes.c_size_t, ctypes.c_size_t, u8p, ctypes.c_size_t, ctypes.c_size_t,
-                                      ctypes.c_int, vp]
-    L.dvc_quality_sync.argtypes = [vp]
-    L.dvc_quality_destroy.argtypes = [vp]
-    L.dvc_quality_destroy.restype = None
-    for name in ("dvc_quality_create", "dvc_quality_compare", "dvc_quality_sync"):
-        getattr(L, name).restype = ctypes.c_int
-    L.dvc_bgr_to_i420.restype = ctypes.c_int
-    for name in ("dvc_of_create", "dvc_of_prime", "dvc_of_step", "dvc_of_step_batch", "dvc_of_sync",
-                 "dvc_of_get_stats", "dvc_of_read_plane", "dvc_of_read_flow", "dvc_of_ktime", "dvc_of_compress"):
-        getattr(L, name).restype = ctypes.c_int
-    for name in ("dvc_device_count", "dvc_fd_create", "dvc_fd_prime", "dvc_fd_step", "dvc_fd_sync",
-                 "dvc_fd_get_stats", "dvc_fd_read_plane", "dvc_fd_ktime", "dvc_gaussian_taps_q8",
-                 "dvc_contour_filter", "dvc_fd_step_batch"):
-        getattr(L, name).restype = ctypes.c_int
-    if L.dvc_abi_version() != ABI_VERSION:
+    if L.dvc_abi_version() != ABI_VERSION:   # (int (void): callable as loaded)
         # a library with another dvc_fd_params / flag layout would corrupt
         # memory: refuse it unless the caller opts in explicitly (A/B of builds
         # from an older tree whose layout is known to match)
@@ -287,6 +238,11 @@ def lib() -> ctypes.CDLL:
                               "(set DVC_ALLOW_ABI_MISMATCH=1 to load it anyway)")
         import warnings
         warnings.warn(f"{path}: ABI version mismatch accepted (DVC_ALLOW_ABI_MISMATCH=1)")
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if name in OPTIONAL and not hasattr(L, name):
+            continue
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -295,6 +251,37 @@ def check(rc: int) -> None:
     if rc != DVC_OK:
         msg = lib().dvc_last_error()
         raise DvcError(rc, msg.decode() if msg else "")
+
+
+class Handle:
+    """Owner of one C-ABI handle: the lifecycle the six handle classes share.
+    ``_h`` is None until :meth:`_create` succeeds and again after :meth:`close`,
+    so an object whose constructor raised closes and collects silently."""
+    _destroy = ""   # the class's dvc_*_destroy
+    _h = None
+
+    def _create(self, create, *args) -> None:
+        """``create(*args, &handle)``; the handle is kept only when the status is DVC_OK."""
+        h = ctypes.c_void_p()
+        check(create(*args, ctypes.byref(h)))
+        self._h = h
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h:
+            getattr(lib(), self._destroy)(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class _Pinned:
@@ -350,17 +337,16 @@ def of_compress(bgr, mask, quant: float = 100.0, device: int = 0):
     return out
 
 
-class OFCompressor:
+class OFCompressor(Handle):
     """compress_with_motion's loop (of:141-185) on the GPU for chunks of frames
     (dvc_ofc): host numpy frames (n, H, W, 3) and decoded masks (n, H, W) or
     (n, H, W, 3) -> compressed frames (n, H, W, 3)."""
 
+    _destroy = "dvc_ofc_destroy"
+
     def __init__(self, width: int, height: int, quant: float = 100.0, max_batch: int = 32, device: int = 0):
         self.W, self.H, self.max_batch = int(width), int(height), max(1, int(max_batch))
-        h = ctypes.c_void_p()
-        check(lib().dvc_ofc_create(self.W, self.H, float(quant), self.max_batch, int(device), None, 0,
-                                   ctypes.byref(h)))
-        self._h = h
+        self._create(lib().dvc_ofc_create, self.W, self.H, float(quant), self.max_batch, int(device), None, 0)
 
     def run(self, frames, masks, out=None):
         import numpy as np
@@ -378,17 +364,6 @@ class OFCompressor:
             check(lib().dvc_ofc_run(self._h, f.ctypes.data, 3 * self.W, f[0].nbytes, m.ctypes.data, self.W * ch,
                                     m[0].nbytes, ch, n, out.ctypes.data, out[0].nbytes))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dvc_ofc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def yuv420_to_bgr(frames, fmt: str = "I420", device: int = 0):
@@ -423,22 +398,22 @@ def bgr_to_i420(frames, device: int = 0):
     return out[0] if one else out
 
 
-class JpegEncoder:
+class JpegEncoder(Handle):
     """cv2.VideoWriter's codec end on the GPU (dvc_jpeg): host numpy frames,
     (n, H, W, 3) BGR or (n, H, W) single-channel, -> one ``bytes`` per frame, the
     frame's JFIF entropy data and EOI; ``header`` (SOI..SOS, constant per
     encoder) in front of it makes a complete baseline JPEG image."""
 
+    _destroy = "dvc_jpeg_destroy"
+
     def __init__(self, width: int, height: int, is_color: bool = True, quality: int = 75, max_batch: int = 8,
                  device: int = 0):
         self.W, self.H, self.is_color = int(width), int(height), bool(is_color)
         self.fmt = FMT_BGR if is_color else FMT_GRAY
-        self._h = self._out = None
-        h = ctypes.c_void_p()
-        check(lib().dvc_jpeg_create(self.W, self.H, self.fmt, int(quality), max(1, int(max_batch)), int(device), None,
-                                    0, ctypes.byref(h)))
-        self._h = h
-        n = ctypes.c_size_t()
+        self._out = None
+        self._create(lib().dvc_jpeg_create, self.W, self.H, self.fmt, int(quality), max(1, int(max_batch)),
+                     int(device), None, 0)
+        h, n = self._h, ctypes.c_size_t()
         check(lib().dvc_jpeg_header(h, None, 0, ctypes.byref(n)))
         buf = (ctypes.c_uint8 * n.value)()
         check(lib().dvc_jpeg_header(h, buf, n.value, ctypes.byref(n)))
@@ -476,19 +451,8 @@ class JpegEncoder:
                 break
         return [out[i, :int(sizes[i])].tobytes() for i in range(n)]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dvc_jpeg_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class JpegDecoder:
+class JpegDecoder(Handle):
     """cv2.VideoCapture's codec end on the GPU (dvc_jpegd): whole JPEG samples
     (``bytes``, as Mp4MjpegReader.read_sample returns them) -> numpy frames,
     (H, W, 3) BGR or (H, W) for a single-component stream, the bytes Pillow
@@ -496,14 +460,13 @@ class JpegDecoder:
     sample's header bytes differ from the last one's; a stream outside the
     decoder's set raises DvcError with code DVC_E_UNSUPPORTED."""
 
+    _destroy = "dvc_jpegd_destroy"
+
     def __init__(self, max_width: int, max_height: int, max_batch: int = 8, device: int = 0):
         self.max_batch = max(1, int(max_batch))
-        self._h = self._in = self._out = None
+        self._in = self._out = None
         self._hdr, self.W, self.H, self.fmt = None, 0, 0, FMT_BGR
-        h = ctypes.c_void_p()
-        check(lib().dvc_jpegd_create(int(max_width), int(max_height), self.max_batch, int(device), None, 0,
-                                     ctypes.byref(h)))
-        self._h = h
+        self._create(lib().dvc_jpegd_create, int(max_width), int(max_height), self.max_batch, int(device), None, 0)
 
     def set_header(self, sample: bytes) -> int:
         """Parse ``sample``'s header; returns its length (where the entropy data starts)."""
@@ -559,23 +522,12 @@ class JpegDecoder:
             run.append(s)
         return frames
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dvc_jpegd_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # dvc_quality_frame (include/dvc.h) as a numpy record
 QUALITY_FRAME = [("sse", "<u8", (4,)), ("ssim_q32", "<i8"), ("windows", "<u4"), ("pixels", "<u4")]
 
 
-class QualityMeter:
+class QualityMeter(Handle):
     """The quality meter on the GPU (dvc_quality): reference and test frames,
     (n, H, W, 3) BGR uint8 with n <= ``max_batch`` — any strides whose pixels are
     3 contiguous bytes and whose rows are >= 3 W bytes apart are read as they
@@ -583,12 +535,11 @@ class QualityMeter:
     ``QUALITY_FRAME`` record per pair: the exact integers DESIGN.md "Quality
     metrics" defines; :mod:`quality` derives PSNR and SSIM from them."""
 
+    _destroy = "dvc_quality_destroy"
+
     def __init__(self, width: int, height: int, device: int = 0, max_batch: int = 8):
         self.W, self.H, self.max_batch = int(width), int(height), int(max_batch)
-        self._h = None
-        h = ctypes.c_void_p()
-        check(lib().dvc_quality_create(self.W, self.H, self.max_batch, int(device), None, 0, ctypes.byref(h)))
-        self._h = h
+        self._create(lib().dvc_quality_create, self.W, self.H, self.max_batch, int(device), None, 0)
 
     def _rows(self, frames):
         """``frames`` as (array, pitch, frame stride) the C-ABI can read in place."""
@@ -612,17 +563,6 @@ class QualityMeter:
         check(lib().dvc_quality_compare(self._h, a.ctypes.data, ap, as_, b.ctypes.data, bp, bs, a.shape[0],
                                         out.ctypes.data))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dvc_quality_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def copy_rate(device: int = 0, nbytes: int = 1 << 30, reps: int = 20, nontemporal: bool = True) -> float:

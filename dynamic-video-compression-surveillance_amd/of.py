@@ -16,8 +16,8 @@ import ctypes
 
 import numpy as np
 
-from . import _buffers as B
 from . import _native as N
+from ._worker import Worker
 
 
 def derive_of_params(width: int, height: int, flow_threshold: float = 0.5, alpha_fraction: float = 0.2,
@@ -48,46 +48,18 @@ def derive_of_params(width: int, height: int, flow_threshold: float = 0.5, alpha
     return p
 
 
-class OFWorker:
+class OFWorker(Worker):
+    _abi, _destroy = "dvc_of", "dvc_of_destroy"
+    _outs = ("mask", "compressed")
+
     def __init__(self, width: int, height: int, *, device: int = 0, stream=None, device_ptrs: bool = False,
                  keep_planes: bool = False, ktiming: bool = False, max_batch: int = 1, **kwargs):
-        flags = (N.DVC_FLAG_DEVICE_PTRS if device_ptrs else 0) | (N.DVC_FLAG_KEEP_PLANES if keep_planes else 0) \
-            | (N.DVC_FLAG_KTIMING if ktiming else 0) | (N.DVC_FLAG_JOIN_STREAM if stream is not None else 0)
-        self.params = derive_of_params(width, height, flags=flags, **kwargs)
-        self.params.max_batch = int(max_batch)
-        self.W, self.H = int(width), int(height)
-        self.in_format = kwargs.get("in_format", "BGR")
-        self.device = int(device)
-        self.device_ptrs = device_ptrs
-        self._lib = N.lib()
-        h = ctypes.c_void_p()
-        s = ctypes.c_void_p(int(stream)) if stream is not None else None
-        N.check(self._lib.dvc_of_create(ctypes.byref(self.params), self.device, s, ctypes.byref(h)))
-        self._h = h
-
-    @property
-    def _fshape(self):
-        """Input frames: packed BGR, or a (H*3/2, W) 4:2:0 frame."""
-        return (self.H, self.W, 3) if self.in_format == "BGR" else (self.H * 3 // 2, self.W)
-
-    @property
-    def _oshape(self):
-        return (self.H, self.W, 3)
-
-    @property
-    def _pitch(self):
-        return 3 * self.W if self.in_format == "BGR" else self.W
-
-    def _dev(self, x, name, tail, n=None, batched=False) -> int:
-        return B.device_buf(x, tail, self.device, name, n=n, batched=batched)
-
-    def prime(self, frame) -> None:
-        """of:54-62: previous gray := gray(frame 0); the vote window is emptied."""
-        if self.device_ptrs:
-            N.check(self._lib.dvc_of_prime(self._h, self._dev(frame, "frame", self._fshape)[0], self._pitch))
-        else:
-            f = B.host_in(frame, self._fshape, "frame")
-            N.check(self._lib.dvc_of_prime(self._h, f.ctypes.data, self._pitch))
+        W, H = int(width), int(height)
+        self._oshape = (H, W, 3)
+        self._astride = (W * H,)   # dvc_of_step_batch: mask_stride
+        self._open(derive_of_params(width, height, flags=0, **kwargs), kwargs.get("in_format", "BGR"), (W, H),
+                   ((H, W), self._oshape), device=device, stream=stream, device_ptrs=device_ptrs,
+                   keep_planes=keep_planes, ktiming=ktiming, max_batch=max_batch)
 
     def set_state(self, prev_gray, raw_masks) -> None:
         """Resume instead of :meth:`prime` (dvc_of_set_state): the previous gray
@@ -106,57 +78,14 @@ class OFWorker:
         """of:70-101 + of:151-183 for one frame. Host mode returns ``(mask,
         compressed)`` (H x W {0,255} and H x W x 3); device mode writes into the
         given buffers and returns None."""
-        if self.device_ptrs:
-            addr = self._dev(frame, "frame", self._fshape)[0]
-            mk = self._dev(mask, "mask", (self.H, self.W))[0] if mask is not None else None
-            cp = self._dev(compressed, "compressed", self._oshape)[0] if compressed is not None else None
-            N.check(self._lib.dvc_of_step(self._h, addr, self._pitch, mk, cp))
-            return None
-        f = B.host_in(frame, self._fshape, "frame")
-        mask = B.host_out(mask, (self.H, self.W), "mask", "mask" in want)
-        compressed = B.host_out(compressed, self._oshape, "compressed", "compressed" in want)
-        N.check(self._lib.dvc_of_step(self._h, f.ctypes.data, self._pitch,
-                                      mask.ctypes.data if mask is not None else None,
-                                      compressed.ctypes.data if compressed is not None else None))
-        return mask, compressed
+        return self._step(frame, mask, compressed, want)
 
     def step_batch(self, frames, mask=None, compressed=None, want=("mask", "compressed")):
         """n consecutive frames (identical to n :meth:`step` calls). Host mode:
         (n, H, W, 3) uint8 in, ``(masks, compressed)`` out. Device mode: CUDA
         tensors on the handle's device or explicit ``(address, n)`` tuples;
         asynchronous, returns None."""
-        fs, ms, os_ = int(np.prod(self._fshape)), self.W * self.H, 3 * self.W * self.H
-        if self.device_ptrs:
-            addr, n = self._dev(frames, "frames", self._fshape, batched=True)
-            mk = self._dev(mask, "mask", (self.H, self.W), n=n, batched=True)[0] if mask is not None else None
-            cp = self._dev(compressed, "compressed", self._oshape, n=n, batched=True)[0] \
-                if compressed is not None else None
-            N.check(self._lib.dvc_of_step_batch(self._h, addr, self._pitch, fs, n, mk, ms, cp, os_))
-            return None
-        if not isinstance(frames, np.ndarray) or frames.ndim != len(self._fshape) + 1:
-            raise ValueError(f"frames: expected uint8 frames of shape (n, {', '.join(map(str, self._fshape))})")
-        n = int(frames.shape[0])
-        f = B.host_in(frames, (n,) + self._fshape, "frames")
-        mask = B.host_out(mask, (n, self.H, self.W), "mask", "mask" in want)
-        compressed = B.host_out(compressed, (n,) + self._oshape, "compressed", "compressed" in want)
-        N.check(self._lib.dvc_of_step_batch(self._h, f.ctypes.data, self._pitch, fs, n,
-                                            mask.ctypes.data if mask is not None else None, ms,
-                                            compressed.ctypes.data if compressed is not None else None, os_))
-        return mask, compressed
-
-    def sync(self) -> None:
-        N.check(self._lib.dvc_of_sync(self._h))
-
-    def stats(self) -> dict:
-        s = N.OfStats()
-        N.check(self._lib.dvc_of_get_stats(self._h, ctypes.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in N.OfStats._fields_}
-
-    def plane(self, which: int) -> np.ndarray:
-        """N.OF_PLANE_*: raw |flow| mask, vote-smoothed, close/open, rectangles, gray."""
-        out = np.empty((self.H, self.W), np.uint8)
-        N.check(self._lib.dvc_of_read_plane(self._h, int(which), out.ctypes.data))
-        return out
+        return self._step_batch(frames, mask, compressed, want)
 
     def flow(self) -> np.ndarray:
         """Farneback flow (H x W x 2 float32) of the last frame (needs keep_planes)."""
@@ -176,13 +105,6 @@ class OFWorker:
         N.check(self._lib.dvc_of_debug_read(self._h, what, level, out.ctypes.data, None, None))
         return out
 
-    def ktime(self, reset: bool = False):
-        """(total ms, launches) of the finest-level Farneback iterations, hipEvent-timed."""
-        ms = ctypes.c_double()
-        n = ctypes.c_uint64()
-        N.check(self._lib.dvc_of_ktime(self._h, ctypes.byref(ms), ctypes.byref(n), 1 if reset else 0))
-        return float(ms.value), int(n.value)
-
     def ktime_kernel(self) -> str:
         """The kernel that ran the level-0 iterations of the last batch (what
         :meth:`ktime` timed): "k_flow" (direct sums), "k_flow_scan" (the
@@ -193,20 +115,3 @@ class OFWorker:
         if k < 0:
             N.check(k)
         return {N.KTIME_FLOW: "k_flow", N.KTIME_FLOW_SCAN: "k_flow_scan", N.KTIME_FLOW_SCAN2: "k_flow_scan2"}[k]
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.dvc_of_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -26,6 +26,175 @@ def test_abi_exports_every_declared_symbol():
     assert L.dvc_abi_version() == dvc_amd._native.ABI_VERSION
 
 
+# ---- the bindings against include/dvc.h, read as text ----------------------
+_C_CLASS = {"int": "i32", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64", "size_t": "u64",
+            "float": "f32", "double": "f64", "void": "void"}
+_SIZE = {"i32": 4, "u32": 4, "f32": 4, "i64": 8, "u64": 8, "f64": 8}
+
+
+def _header():
+    src = open(os.path.join(ROOT, "include", "dvc.h")).read()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+
+
+def _c_class(decl, named):
+    """The class of a C return type, or of a parameter / field declaration with its name."""
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.split() if w != "const"]
+    return _C_CLASS[" ".join(words[:-1] if named else words)]
+
+
+def _ctypes_class(t):
+    import ctypes
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    if issubclass(t, ctypes.Array):
+        return f"{_ctypes_class(t._type_)}[{t._length_}]"
+    return {ctypes.c_int: "i32", ctypes.c_uint32: "u32", ctypes.c_int64: "i64", ctypes.c_uint64: "u64",
+            ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]   # (c_int32 is c_int, c_size_t is c_uint64)
+
+
+def _header_prototypes():
+    """{name: [return class, parameter classes...]} of every dvc_* prototype."""
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(dvc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header()):
+        params = [p for p in params.split(",") if p.strip() != "void"]
+        protos[name] = [_c_class(ret, False)] + [_c_class(p, True) for p in params]
+    return protos
+
+
+def _signature_mismatches(protos, table):
+    """Names whose table entry is missing or differs in class from the header's prototype."""
+    def classes(restype, argtypes):
+        return [_ctypes_class(restype)] + [_ctypes_class(t) for t in argtypes]
+    return sorted(n for n in set(protos) | set(table) if n not in table or protos.get(n) != classes(*table[n]))
+
+
+def _header_struct(name):
+    """[(field, class)] of ``typedef struct name`` and its size under natural alignment."""
+    body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), _header(), re.S).group(1)
+    fields, size, align = [], 0, 1
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        m = re.fullmatch(r"(.*?\w)\s*(?:\[(\d+)\])?", decl, re.S)
+        cls, count = _c_class(m.group(1), True), int(m.group(2) or 1)
+        fields.append((m.group(1).split()[-1], cls if m.group(2) is None else f"{cls}[{count}]"))
+        size = -(-size // _SIZE[cls]) * _SIZE[cls] + count * _SIZE[cls]
+        align = max(align, _SIZE[cls])
+    return fields, -(-size // align) * align
+
+
+def test_signature_table_matches_every_prototype():
+    """Return type and every parameter of each include/dvc.h prototype, classed
+    as pointer / int / uint32_t / int64_t / uint64_t = size_t / float / double /
+    void, equal the classes of the function's entry in _native.SIGNATURES."""
+    import dvc_amd
+    N = dvc_amd._native
+    protos = _header_prototypes()
+    assert len(protos) == len(N.EXPORTS) == 55 and set(protos) == set(_declared_symbols())
+    assert list(protos) == N.EXPORTS            # the table is in the header's order
+    assert _signature_mismatches(protos, N.SIGNATURES) == []
+    N.build()
+    L = N.lib()
+    for name, (restype, argtypes) in N.SIGNATURES.items():   # lib() binds what the table says
+        assert getattr(L, name).restype is restype and tuple(getattr(L, name).argtypes) == tuple(argtypes), name
+    assert set(N.OPTIONAL) <= set(N.SIGNATURES)
+
+
+def test_signature_check_detects_a_wrong_entry():
+    """The comparison reports an entry with an argument dropped and one with a
+    size_t bound as an int (tables compared in process; nothing is called)."""
+    import ctypes
+    import dvc_amd
+    N = dvc_amd._native
+    protos = _header_prototypes()
+    restype, argtypes = N.SIGNATURES["dvc_fd_step_batch"]
+    dropped = dict(N.SIGNATURES, dvc_fd_step_batch=(restype, argtypes[:-1]))
+    assert _signature_mismatches(protos, dropped) == ["dvc_fd_step_batch"]
+    restype, argtypes = N.SIGNATURES["dvc_of_prime"]
+    assert argtypes[2] is ctypes.c_size_t
+    narrowed = dict(N.SIGNATURES, dvc_of_prime=(restype, argtypes[:2] + (ctypes.c_int,)))
+    assert _signature_mismatches(protos, narrowed) == ["dvc_of_prime"]
+    missing = {k: v for k, v in N.SIGNATURES.items() if k != "dvc_copy_rate"}
+    assert _signature_mismatches(protos, missing) == ["dvc_copy_rate"]
+
+
+def test_structs_match_the_header():
+    import ctypes
+    import dvc_amd
+    N = dvc_amd._native
+    for cname, cls in (("dvc_fd_params", N.FdParams), ("dvc_of_params", N.OfParams), ("dvc_fd_stats", N.FdStats),
+                       ("dvc_of_stats", N.FdStats)):
+        fields, size = _header_struct(cname)
+        assert [(n, _ctypes_class(t)) for n, t in cls._fields_] == fields, cname
+        assert ctypes.sizeof(cls) == size, cname
+    assert N.OfStats is N.FdStats
+    fields, size = _header_struct("dvc_quality_frame")
+    np_class = {"<u8": "u64", "<i8": "i64", "<u4": "u32"}
+    assert [(f[0], np_class[f[1]] + (f"[{f[2][0]}]" if len(f) > 2 else "")) for f in N.QUALITY_FRAME] == fields
+    assert fields[0] == ("sse", "u64[4]")
+    dt = np.dtype(N.QUALITY_FRAME)
+    assert dt.itemsize == size == 48
+    assert [dt.fields[n][1] for n, _ in fields] == [0, 32, 40, 44]   # numpy packs: the natural offsets, no padding
+
+
+# a #define of the header without a Python twin, and why
+_DEFINES_WITHOUT_TWIN = {"DVC_H": "the include guard: no value"}
+
+
+def test_constants_match_the_header():
+    """Every #define of the header equals its twin in _native: DVC_FLAG_*, DVC_E_*
+    and DVC_OK under their own names, the others without the DVC_ prefix."""
+    import dvc_amd
+    N = dvc_amd._native
+    defines = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(DVC_\w+)[ \t]*(\S*)", _header(), re.M)
+    assert len(defines) > 30
+    checked = set()
+    for name, value in defines:
+        if name in _DEFINES_WITHOUT_TWIN:
+            continue
+        twin = name if name.startswith(("DVC_FLAG_", "DVC_E_")) or name == "DVC_OK" else name[len("DVC_"):]
+        assert hasattr(N, twin), f"{name}: no {twin} in _native"
+        assert getattr(N, twin) == int(value.rstrip("uU"), 0), name
+        checked.add(name)
+    for family in ("DVC_FLAG_", "DVC_E_", "DVC_FMT_", "DVC_PLANE_", "DVC_OF_PLANE_", "DVC_KTIME_"):
+        assert any(n.startswith(family) for n in checked), family
+    assert {"DVC_OK", "DVC_ABI_VERSION", "DVC_MAX_BATCH"} <= checked
+    assert N.FORMATS == {"BGR": N.FMT_BGR, "I420": N.FMT_I420, "NV12": N.FMT_NV12}
+
+
+def test_failed_create_leaves_a_silent_object():
+    """Each handle class refuses width 0 in its create, before any HIP call, with
+    the status pinned here (the quality meter's is DVC_E_UNSUPPORTED: a frame
+    under 8 x 8 has no SSIM window); closing and collecting the object whose
+    constructor raised is silent."""
+    import gc
+    import sys
+    import dvc_amd
+    N = dvc_amd._native
+    N.build()
+    cases = [(dvc_amd.FDWorker, N.DVC_E_INVALID), (dvc_amd.OFWorker, N.DVC_E_INVALID),
+             (N.OFCompressor, N.DVC_E_INVALID), (N.JpegEncoder, N.DVC_E_INVALID),
+             (N.JpegDecoder, N.DVC_E_INVALID), (N.QualityMeter, N.DVC_E_UNSUPPORTED)]
+    unraisable = []
+    hook, sys.unraisablehook = sys.unraisablehook, unraisable.append
+    try:
+        for cls, code in cases:
+            obj = cls.__new__(cls)
+            with pytest.raises(N.DvcError) as e:
+                obj.__init__(0, 48)
+            assert e.value.code == code, cls.__name__
+            obj.close()
+            obj.close()
+            del obj, e
+            gc.collect()
+    finally:
+        sys.unraisablehook = hook
+    assert not unraisable, [str(u.exc_value) for u in unraisable]
+
+
 def test_shipping_library_has_no_result_changing_knobs():
     """The stage-skip ablations (outputs wrong by design) and the CU-split
     experiment live only in variant builds (tools/build_variant.sh

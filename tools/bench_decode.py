@@ -7,50 +7,13 @@ with --kernels, from a second run of this script under rocprofv3 --kernel-trace
 --stats — the time of each kernel per batch.
   python tools/bench_decode.py [--kernels] [--out FILE] [--width W --height H --batch B --quality Q]
 """
-import argparse
-import csv
 import ctypes
-import glob
-import json
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
-sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
-
-
-def kernel_times(a):
-    """{kernel: microseconds per launch} from a profiled child run (3 steps)."""
-    d = tempfile.mkdtemp(prefix="dvc_jpegd_prof_")
-    try:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "t", "--output-format", "csv", "--",
-               sys.executable, os.path.abspath(__file__), "--steps", "3", "--runs", "1",
-               "--width", str(a.width), "--height", str(a.height), "--batch", str(a.batch), "--quality", str(a.quality)]
-        subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, timeout=300)
-        out = {}
-        for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            for row in csv.DictReader(open(path)):
-                if "k_jpegd_" in row["Name"]:
-                    name = "k_jpegd_" + row["Name"].split("k_jpegd_")[1].split("(")[0].split("<")[0]
-                    out[name] = {"us_per_launch": round(float(row["AverageNs"]) / 1e3, 1), "launches": int(row["Calls"])}
-        return out
-    finally:
-        shutil.rmtree(d, ignore_errors=True)
+from codec_bench import child_args, emit, kernel_times, parser, time_calls
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--quality", type=int, default=75)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--kernels", action="store_true")
-    ap.add_argument("--out", default="")
+    ap = parser()
     a = ap.parse_args()
 
     import numpy as np
@@ -83,19 +46,7 @@ def main():
         N.check(L.dvc_jpegd_decode(h, data.data_ptr(), stride, sizes.data_ptr(), B, out.data_ptr(), 3 * W, 3 * W * H,
                                    status.data_ptr()))
 
-    with torch.cuda.stream(s):
-        for _ in range(a.warmup):
-            call()
-        s.synchronize()
-        ms = []
-        for _ in range(a.runs):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            for _ in range(a.steps):
-                call()
-            e1.record(s)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1) / a.steps)
+    ms = time_calls(s, call, a.warmup, a.runs, a.steps)
     N.check(L.dvc_jpegd_sync(h))
     L.dvc_jpegd_destroy(h)
     assert not status.cpu().numpy().any()
@@ -114,12 +65,8 @@ def main():
         "compressed_bytes_per_frame": round(in_bytes / B), "bits_per_pixel": round(8 * in_bytes / px, 3),
     }
     if a.kernels:
-        res["kernels"] = kernel_times(a)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+        res["kernels"] = kernel_times(__file__, "k_jpegd_", child_args(a))
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

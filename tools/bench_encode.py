@@ -7,51 +7,14 @@ second run of this script under rocprofv3 --kernel-trace --stats — the time of
 each kernel per batch.
   python tools/bench_encode.py [--kernels] [--out FILE] [--width W --height H --batch B --quality Q]
 """
-import argparse
-import csv
 import ctypes
-import glob
-import json
-import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
-sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
-
-
-def kernel_times(a):
-    """{kernel: microseconds per launch} from a profiled child run (3 steps)."""
-    d = tempfile.mkdtemp(prefix="dvc_jpeg_prof_")
-    try:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "t", "--output-format", "csv", "--",
-               sys.executable, os.path.abspath(__file__), "--steps", "3", "--runs", "1", "--no-copy-rate",
-               "--width", str(a.width), "--height", str(a.height), "--batch", str(a.batch), "--quality", str(a.quality)]
-        subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, timeout=300)
-        out = {}
-        for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            for row in csv.DictReader(open(path)):
-                if "k_jpeg_" in row["Name"]:
-                    name = "k_jpeg_" + row["Name"].split("k_jpeg_")[1].split("(")[0].split("<")[0]
-                    out[name] = {"us_per_launch": round(float(row["AverageNs"]) / 1e3, 1), "launches": int(row["Calls"])}
-        return out
-    finally:
-        shutil.rmtree(d, ignore_errors=True)
+from codec_bench import child_args, emit, kernel_times, parser, time_calls
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--quality", type=int, default=75)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--runs", type=int, default=5)
-    ap.add_argument("--kernels", action="store_true")
+    ap = parser()
     ap.add_argument("--no-copy-rate", action="store_true")
-    ap.add_argument("--out", default="")
     a = ap.parse_args()
 
     import numpy as np
@@ -76,19 +39,7 @@ def main():
     def call():
         N.check(L.dvc_jpeg_encode(h, frames.data_ptr(), 3 * W, 3 * W * H, B, out.data_ptr(), stride, sizes.data_ptr()))
 
-    with torch.cuda.stream(s):
-        for _ in range(a.warmup):
-            call()
-        s.synchronize()
-        ms = []
-        for _ in range(a.runs):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            for _ in range(a.steps):
-                call()
-            e1.record(s)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1) / a.steps)
+    ms = time_calls(s, call, a.warmup, a.runs, a.steps)
     N.check(L.dvc_jpeg_sync(h))
     L.dvc_jpeg_destroy(h)
     out_bytes = int(sizes.cpu().numpy().astype(np.int64).sum())
@@ -114,12 +65,8 @@ def main():
         res["copy_rate_GBps"] = round(N.copy_rate(0), 1)
         res["pipeline_frac_of_copy_rate"] = round(res["pipeline_GBps"] / res["copy_rate_GBps"], 4)
     if a.kernels:
-        res["kernels"] = kernel_times(a)
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+        res["kernels"] = kernel_times(__file__, "k_jpeg_", child_args(a, "--no-copy-rate"))
+    emit(res, a.out)
 
 
 if __name__ == "__main__":
