@@ -340,13 +340,22 @@ def of_compress(bgr, mask, quant: float = 100.0, device: int = 0):
 class OFCompressor(Handle):
     """compress_with_motion's loop (of:141-185) on the GPU for chunks of frames
     (dvc_ofc): host numpy frames (n, H, W, 3) and decoded masks (n, H, W) or
-    (n, H, W, 3) -> compressed frames (n, H, W, 3)."""
+    (n, H, W, 3) -> compressed frames (n, H, W, 3), or with
+    ``out_format="I420"`` (DVC_FLAG_OUT_I420; W and H even) the encoder's 4:2:0
+    frames (n, H*3/2, W)."""
 
     _destroy = "dvc_ofc_destroy"
 
-    def __init__(self, width: int, height: int, quant: float = 100.0, max_batch: int = 32, device: int = 0):
+    def __init__(self, width: int, height: int, quant: float = 100.0, max_batch: int = 32, device: int = 0,
+                 out_format: str = "BGR"):
+        if out_format not in ("BGR", "I420"):
+            raise ValueError(f"out_format {out_format!r}: BGR or I420")
+        self.out_format = out_format
         self.W, self.H, self.max_batch = int(width), int(height), max(1, int(max_batch))
-        self._create(lib().dvc_ofc_create, self.W, self.H, float(quant), self.max_batch, int(device), None, 0)
+        self._oshape = (self.H, self.W, 3) if out_format == "BGR" else (self.H * 3 // 2, self.W)
+        self._obytes = self._oshape[0] * self._oshape[1] * (3 if out_format == "BGR" else 1)
+        self._create(lib().dvc_ofc_create, self.W, self.H, float(quant), self.max_batch, int(device), None,
+                     DVC_FLAG_OUT_I420 if out_format == "I420" else 0)
 
     def run(self, frames, masks, out=None):
         import numpy as np
@@ -359,10 +368,12 @@ class OFCompressor(Handle):
         if f.shape[1:] != (self.H, self.W, 3) or m.shape[:3] != (n, self.H, self.W):
             raise ValueError(f"frames {f.shape} / masks {m.shape} do not match {self.W}x{self.H}")
         if out is None:
-            out = np.empty_like(f)
+            out = np.empty((n,) + self._oshape, np.uint8)
+        elif out.dtype != np.uint8 or out.size != n * self._obytes or not out.flags.c_contiguous:
+            raise ValueError(f"out: expected a contiguous uint8 array of shape {(n,) + self._oshape}")
         if n:
             check(lib().dvc_ofc_run(self._h, f.ctypes.data, 3 * self.W, f[0].nbytes, m.ctypes.data, self.W * ch,
-                                    m[0].nbytes, ch, n, out.ctypes.data, out[0].nbytes))
+                                    m[0].nbytes, ch, n, out.ctypes.data, self._obytes))
         return out
 
 

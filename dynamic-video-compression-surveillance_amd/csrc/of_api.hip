@@ -175,6 +175,8 @@ struct dvc_of {
     int max_batch = 1;
     int ip = 0;                          // row pitch the kernels read BGR frames with: 3 * roundup(W, 4)
     int fmt = DVC_FMT_BGR, crows = 0;   // frame format handed to prime/step (DVC_FMT_*)
+    bool out_i420 = false;               // DVC_FLAG_OUT_I420: compressed frames as I420
+    size_t ofb = 0;                      // bytes of one compressed frame: 3 W H, or W H 3/2 as I420
     long long a_next = 1;
     bool primed = false;
     uint64_t frames = 0;
@@ -294,6 +296,8 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
         return fail(DVC_E_INVALID, "in_format %d unknown", p.in_format);
     if (p.in_format != DVC_FMT_BGR && p.chroma_rows && (p.chroma_rows < p.height || (p.chroma_rows & 1)))
         return fail(DVC_E_INVALID, "chroma_rows %d: even and >= the frame height %d", p.chroma_rows, p.height);
+    if ((p.flags & DVC_FLAG_OUT_I420) && ((p.width | p.height) & 1))
+        return fail(DVC_E_UNSUPPORTED, "I420 outputs need an even width and height (%dx%d)", p.width, p.height);
     // pyramid depth (oc_fb_levels: min size 32)
     int L = 0;
     {
@@ -311,6 +315,8 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
     h->max_batch = p.max_batch == 0 ? 1 : (int)p.max_batch;
     h->fmt = p.in_format;
     h->crows = p.chroma_rows ? p.chroma_rows : p.height;
+    h->out_i420 = p.flags & DVC_FLAG_OUT_I420;
+    h->ofb = h->out_i420 ? (size_t)p.width * p.height * 3 / 2 : (size_t)p.width * p.height * 3;
     const int mb = h->max_batch;
     dvc::OfGeom& g = h->g;
     g.W = p.width;
@@ -521,10 +527,10 @@ int dvc_of_create(const dvc_of_params* prm, int device, void* hip_stream, dvc_of
         const size_t FI = h->fmt == DVC_FMT_BGR ? FS : 3 * N;   // packed host frame (YUV: 1.5 N bytes used)
         if ((e = h->mem.alloc(&h->d_in, FI * mb)) != hipSuccess) return bad(e, "hipMalloc");
         if ((e = h->mem.alloc(&h->d_mask, N * mb)) != hipSuccess) return bad(e, "hipMalloc");
-        if ((e = h->mem.alloc(&h->d_cp, 3 * N * mb)) != hipSuccess) return bad(e, "hipMalloc");
+        if ((e = h->mem.alloc(&h->d_cp, h->ofb * mb)) != hipSuccess) return bad(e, "hipMalloc");
         if ((e = h->mem.alloc_pinned(&h->h_in, FI * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
         if ((e = h->mem.alloc_pinned(&h->h_mask, N * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
-        if ((e = h->mem.alloc_pinned(&h->h_cp, 3 * N * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
+        if ((e = h->mem.alloc_pinned(&h->h_cp, h->ofb * mb)) != hipSuccess) return bad(e, "hipHostMalloc");
     }
     if ((e = hipMemsetAsync(b.stats, 0, 8 * 4 * 64, h->stream)) != hipSuccess) return bad(e, "hipMemset");
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return bad(e, "hipStreamSynchronize");
@@ -725,7 +731,7 @@ static int of_enqueue(dvc_of* h, const uint8_t* d, int dp, size_t fstride, int n
     o.qinv = 1.0 / (double)h->p.quant;
     o.M = h->M;
     o.sf = sf;
-    if (!(skip & 8)) HIP_OK(dvc::of_launch_out(h->g, h->b, o, n, h->s_mask));
+    if (!(skip & 8)) HIP_OK(dvc::of_launch_out(h->g, h->b, o, n, h->s_mask, h->out_i420));
     HIP_OK(hipEventRecord(S.ev_mask, h->s_mask));
     S.recorded = true;
     h->seq++;
@@ -746,7 +752,8 @@ static int of_run(dvc_of* h, const uint8_t* bgr, size_t pitch, size_t fstride, i
     if (!dvc_host::pitch_ok(h->frame(), pitch)) return fail(DVC_E_INVALID, "pitch %zu invalid", pitch);
     if (n > 1 && fstride < dvc_host::frame_span(h->frame(), pitch)) return fail(DVC_E_INVALID, "frame stride %zu invalid", fstride);
     if (n > 1 && mask && mstride < N) return fail(DVC_E_INVALID, "mask stride %zu invalid", mstride);
-    if (n > 1 && compressed && ostride < 3 * N) return fail(DVC_E_INVALID, "output frame stride %zu invalid", ostride);
+    const size_t OB = h->ofb;   // one compressed frame: packed BGR, or I420 (DVC_FLAG_OUT_I420)
+    if (n > 1 && compressed && ostride < OB) return fail(DVC_E_INVALID, "output frame stride %zu invalid", ostride);
     HIP_OK(hipSetDevice(h->device));
     HIP_OK(h->wait_user());
     const bool devp = h->p.flags & DVC_FLAG_DEVICE_PTRS;
@@ -765,14 +772,14 @@ static int of_run(dvc_of* h, const uint8_t* bgr, size_t pitch, size_t fstride, i
             dvc_host::pack_host_frame(h->frame(), in + (size_t)t * fstride, pitch, h->h_in + (size_t)t * FI, h->ip);
         HIP_OK(hipMemcpyAsync(h->d_in, h->h_in, (size_t)m * FI, hipMemcpyHostToDevice, h->s_pyr));
         int rc = of_enqueue(h, h->d_in, (int)(yuv ? W : h->ip), FI, m, mk ? h->d_mask : nullptr, N,
-                            cp ? h->d_cp : nullptr, 3 * N, (int)H);
+                            cp ? h->d_cp : nullptr, OB, (int)H);
         if (rc) return rc;
         if (mk) HIP_OK(hipMemcpyAsync(h->h_mask, h->d_mask, (size_t)m * N, hipMemcpyDeviceToHost, h->s_mask));
-        if (cp) HIP_OK(hipMemcpyAsync(h->h_cp, h->d_cp, (size_t)m * 3 * N, hipMemcpyDeviceToHost, h->s_mask));
+        if (cp) HIP_OK(hipMemcpyAsync(h->h_cp, h->d_cp, (size_t)m * OB, hipMemcpyDeviceToHost, h->s_mask));
         HIP_OK(h->sync());
         for (int t = 0; t < m; ++t) {
             if (mk) std::memcpy(mk + (size_t)t * mstride, h->h_mask + (size_t)t * N, N);
-            if (cp) std::memcpy(cp + (size_t)t * ostride, h->h_cp + (size_t)t * 3 * N, 3 * N);
+            if (cp) std::memcpy(cp + (size_t)t * ostride, h->h_cp + (size_t)t * OB, OB);
         }
     }
     HIP_OK(of_join_user(h));
@@ -922,6 +929,7 @@ struct dvc_ofc {
     int W = 0, H = 0, WW = 0, ip = 0, device = 0, max_batch = 1;
     uint32_t flags = 0;
     float quant = 100.f;
+    size_t ofb = 0;   // bytes of one output frame: 3 W H, or W H 3/2 as I420 (DVC_FLAG_OUT_I420)
     dvc_host::HandleStream stream;   // the caller's, or our own when create's hip_stream is NULL
     dvc_host::DevMem mem;
     uint8_t *fin = nullptr, *d_mask = nullptr, *d_out = nullptr;
@@ -939,6 +947,8 @@ int dvc_ofc_create(int width, int height, float quant, int max_batch, int device
     if (!(quant == quant) || quant == 0.0f) return fail(DVC_E_INVALID, "quant must be nonzero");
     if (max_batch < 0 || max_batch > DVC_MAX_BATCH) return fail(DVC_E_INVALID, "max_batch %d outside 1..%d", max_batch,
                                                                 DVC_MAX_BATCH);
+    if ((flags & DVC_FLAG_OUT_I420) && ((width | height) & 1))
+        return fail(DVC_E_UNSUPPORTED, "I420 outputs need an even width and height (%dx%d)", width, height);
     HIP_OK(hipSetDevice(device));
     dvc_ofc* h = new dvc_ofc();
     h->W = width;
@@ -949,6 +959,7 @@ int dvc_ofc_create(int width, int height, float quant, int max_batch, int device
     h->max_batch = max_batch ? max_batch : 1;
     h->flags = flags;
     h->quant = quant;
+    h->ofb = (flags & DVC_FLAG_OUT_I420) ? (size_t)width * height * 3 / 2 : (size_t)width * height * 3;
     dvc_host::dct_matrix(8, h->M);
     const size_t W = width, H = height, mb = h->max_batch;
     // (a NULL hip_stream always means a stream of our own: DVC_FLAG_JOIN_STREAM is not looked at)
@@ -957,7 +968,7 @@ int dvc_ofc_create(int width, int height, float quant, int max_batch, int device
     if (e == hipSuccess) e = h->mem.alloc(&h->fin, (size_t)h->ip * H * mb);   // staged / re-pitched frames
     if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
         e = h->mem.alloc(&h->d_mask, 3 * W * H * mb);
-        if (e == hipSuccess) e = h->mem.alloc(&h->d_out, 3 * W * H * mb);
+        if (e == hipSuccess) e = h->mem.alloc(&h->d_out, h->ofb * mb);
     }
     if (e != hipSuccess) {
         delete h;
@@ -973,10 +984,10 @@ int dvc_ofc_run(dvc_ofc* h, const uint8_t* bgr, size_t pitch, size_t frame_strid
     if (!h || !bgr || !mask || !out) return fail(DVC_E_INVALID, "NULL argument");
     if (n < 0) return fail(DVC_E_INVALID, "negative frame count");
     if (mask_channels != 1 && mask_channels != 3) return fail(DVC_E_INVALID, "mask_channels %d: 1 or 3", mask_channels);
-    const size_t W = h->W, H = h->H, N = W * H, FS = (size_t)h->ip * H;
+    const size_t W = h->W, H = h->H, OB = h->ofb, FS = (size_t)h->ip * H;
     if (pitch < 3 * W || mask_pitch < W * mask_channels) return fail(DVC_E_INVALID, "pitch invalid");
     if (n > 1 && (frame_stride < pitch * (H - 1) + 3 * W || mask_stride < mask_pitch * (H - 1) + W * mask_channels ||
-                  out_stride < 3 * N))
+                  out_stride < OB))
         return fail(DVC_E_INVALID, "frame / mask / output stride invalid");
     HIP_OK(hipSetDevice(h->device));
     const bool devp = h->flags & DVC_FLAG_DEVICE_PTRS;
@@ -1022,14 +1033,14 @@ int dvc_ofc_run(dvc_ofc* h, const uint8_t* bgr, size_t pitch, size_t frame_strid
         a.mbits = h->bits;
         a.mbstride = H * h->WW;
         a.compressed = devp ? o : h->d_out;
-        a.ostride = devp ? out_stride : 3 * N;
+        a.ostride = devp ? out_stride : OB;
         a.quant = h->quant;
         a.qinv = 1.0 / (double)h->quant;
         a.M = h->M;
-        HIP_OK(dvc::of_launch_out(g, b, a, m, st));
+        HIP_OK(dvc::of_launch_out(g, b, a, m, st, h->flags & DVC_FLAG_OUT_I420));
         if (!devp) {
             for (int t = 0; t < m; ++t)
-                HIP_OK(hipMemcpyAsync(o + (size_t)t * out_stride, h->d_out + t * 3 * N, 3 * N, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipMemcpyAsync(o + (size_t)t * out_stride, h->d_out + t * OB, OB, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
         }
     }

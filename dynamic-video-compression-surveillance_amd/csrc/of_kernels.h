@@ -118,7 +118,7 @@ struct OfOutArgs {
     size_t mstride;
     const uint64_t* mbits; // nullable: the gating mask as bits (H x WW per frame at t*mbstride) instead
     size_t mbstride;       //   of b.rbits (dvc_ofc: a decoded mask.mp4, of:141-149)
-    uint8_t* compressed;   // nullable: frame t at compressed + t*ostride, rows of 3W
+    uint8_t* compressed;   // nullable: frame t at compressed + t*ostride, rows of 3W (or I420: of_launch_out)
     size_t ostride;
     float quant;
     double qinv;           // RN53(1 / (double)quant), see div_rn
@@ -149,7 +149,11 @@ hipError_t of_launch_mask(const OfGeom& g, const OfBufs& b, long long a0, int wi
 // the LDS one row of the mask stage needs (morph_kernel and the width set it): create refuses more than the device has
 size_t of_mask_min_lds(const OfGeom& g);
 // compress_with_motion (of:151-183) + the mask bytes
-hipError_t of_launch_out(const OfGeom& g, const OfBufs& b, const OfOutArgs& o, int n, hipStream_t s);
+// i420 (DVC_FLAG_OUT_I420; W and H even): frame t at o.compressed + t*o.ostride is
+// cvtColor BGR2YUV_I420 of that BGR frame — a W x H Y plane, then U and V planes
+// of W/2 x H/2 in rows of W/2, W*H*3/2 bytes
+hipError_t of_launch_out(const OfGeom& g, const OfBufs& b, const OfOutArgs& o, int n, hipStream_t s,
+                         bool i420 = false);
 // a decoded mask plane (1 or 3 channels, rows of mpitch, frames of mstride) ->
 // nonzero-after-BGR2GRAY bits, H x WW words per frame (of:147-149)
 hipError_t of_launch_mask_bits(const uint8_t* mask, size_t mpitch, size_t mstride, int channels, int W, int H, int n,

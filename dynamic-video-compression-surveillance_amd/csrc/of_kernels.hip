@@ -2194,6 +2194,13 @@ __device__ __forceinline__ void transpose8(float* S, int r, const float (&v)[8],
     for (int i = 0; i < 8; ++i) out[i] = S[i * 9 + r];
 }
 
+// OI: the compressed frame as the encoder's I420 input (DVC_FLAG_OUT_I420,
+// cvtColor BGR2YUV_I420 of the BGR frame: yuv_px.h) as a template parameter, so
+// the BGR instantiation carries none of it. The lane's 8 luma bytes go out as
+// two dwords; lanes of even rows hold the top-left pixel of each 2x2 quad at
+// j = 0, 2, 4, 6 and store its 4 U and 4 V samples — no cross-lane traffic.
+// (A static block is grey, so its chroma is 128: the general form gives that.)
+template <bool OI>
 __global__ void __launch_bounds__(256) k_of_out(OfGeom g, OfBufs B, OfOutArgs o)
 {
     __shared__ float sT[4][8][72];
@@ -2315,6 +2322,49 @@ __global__ void __launch_bounds__(256) k_of_out(OfGeom g, OfBufs B, OfOutArgs o)
         channel(ch[2]);
     }
     if (!act) return;
+    if constexpr (OI) {
+        uint32_t yo[8], uo[4], vo[4];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {   // as below, then BGR2YUV_I420 of the pixel
+            const int yv = ch[0][j], cr = ch[1][j] - 128, cb = ch[2][j] - 128;
+            uint32_t b = satu8(yv + descale14(cb * 29049));
+            uint32_t gg = satu8(yv + descale14(cb * -5636 + cr * -11698));
+            uint32_t rr = satu8(yv + descale14(cr * 22987));
+            if (sfull) b = gg = rr = gray_px(b, gg, rr);
+            yo[j] = yuvpx::luma((int)b, (int)gg, (int)rr);
+            if (!(j & 1)) {
+                uo[j >> 1] = yuvpx::chroma_u((int)b, (int)gg, (int)rr);
+                vo[j >> 1] = yuvpx::chroma_v((int)b, (int)gg, (int)rr);
+            }
+        }
+        // frame t: Y plane W x H, then U and V planes of W/2 x H/2 (W, H even: np is even)
+        uint8_t* f = o.compressed + (size_t)t * o.ostride;
+        uint8_t* yp = f + (size_t)y * W + bx;
+        if (np == 8 && ((uintptr_t)yp & 3) == 0) {
+            uint32_t* d = reinterpret_cast<uint32_t*>(yp);
+            d[0] = yuvpx::pack4(yo[0], yo[1], yo[2], yo[3]);
+            d[1] = yuvpx::pack4(yo[4], yo[5], yo[6], yo[7]);
+        } else {   // rows of W bytes: W % 4 != 0 leaves odd rows unaligned
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < np) yp[j] = (uint8_t)yo[j];
+        }
+        if (y & 1) return;
+        uint8_t* up = f + (size_t)W * H + (size_t)(y >> 1) * (W >> 1) + (bx >> 1);
+        uint8_t* vp = up + (size_t)(W >> 1) * (H >> 1);
+        if (np == 8 && (((uintptr_t)up | (uintptr_t)vp) & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(up) = yuvpx::pack4(uo[0], uo[1], uo[2], uo[3]);
+            *reinterpret_cast<uint32_t*>(vp) = yuvpx::pack4(vo[0], vo[1], vo[2], vo[3]);
+        } else {   // chroma rows of W/2 bytes: W % 8 != 0
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (2 * k < np) {
+                    up[k] = (uint8_t)uo[k];
+                    vp[k] = (uint8_t)vo[k];
+                }
+        }
+        return;
+    }
     uint8_t ob[24];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {   // YCrCb -> BGR (of:170-171); static blocks -> gray -> BGR (of:174-183)
@@ -2718,13 +2768,17 @@ hipError_t of_launch_mask(const OfGeom& g, const OfBufs& b, long long a0, int wi
     return hipGetLastError();
 }
 
-hipError_t of_launch_out(const OfGeom& g, const OfBufs& b, const OfOutArgs& o, int n, hipStream_t s)
+hipError_t of_launch_out(const OfGeom& g, const OfBufs& b, const OfOutArgs& o, int n, hipStream_t s, bool i420)
 {
     if (!o.mask && !o.compressed) return hipSuccess;
     if (!dct8_is_const(o.M)) return hipErrorInvalidValue;   // k_of_out's constant basis
     const int nbx = (g.W + 7) / 8, nby = (g.H + 7) / 8;   // partial edge blocks included (pixels, not DCT)
     dim3 grid((nbx + 7) / 8, (nby + 3) / 4, n);
-    hipLaunchKernelGGL(k_of_out, grid, dim3(256), 0, s, g, b, o);
+    if (i420 && ((g.W | g.H) & 1)) return hipErrorInvalidValue;   // 4:2:0: whole 2x2 quads (refused at create)
+    if (i420)
+        hipLaunchKernelGGL(k_of_out<true>, grid, dim3(256), 0, s, g, b, o);
+    else
+        hipLaunchKernelGGL(k_of_out<false>, grid, dim3(256), 0, s, g, b, o);
     return hipGetLastError();
 }
 

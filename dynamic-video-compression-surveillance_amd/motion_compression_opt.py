@@ -24,7 +24,9 @@ The per-frame work runs on the GPU: ``OFWorker`` (Farneback, vote, close/open,
 rectangles; of:70-97) and ``OFCompressor`` / ``dvc_ofc_run`` (of:141-185) —
 never a CPU fallback. Both loops run in chunks through ``ChunkPipeline``
 (reader / GPU / writer threads). ``avg_s`` is total / frames, as of:106,190
-compute it.
+compute it. Y4M sinks of even sides (``DVC_VIDEO_SINK=y4m``) take I420 frames
+as they are: ``compressed`` straight from the compressor
+(``out_format="I420"``), ``overlay`` from one conversion call per chunk.
 """
 from __future__ import annotations
 
@@ -65,6 +67,13 @@ def _device() -> int:
     return int(os.environ.get("DVC_DEVICE", os.environ.get("LOCAL_RANK", 0)))
 
 
+def _yuv_sink(sink, width, height) -> bool:
+    """A Y4M colour sink of even sides takes I420 frames as they are
+    (``write_yuv``): no BGR round trip through the host, no conversion of one
+    frame at a time inside ``Y4mWriter.write``."""
+    return isinstance(sink, video_io.Y4mWriter) and width % 2 == 0 and height % 2 == 0
+
+
 def temporal_smoothing_flow(video_path, output_dir, flow_threshold=0.5, alpha_fraction=0.2,
                             window_size=30, morph_kernel=2, save_name="overlay.mp4",
                             mask_save_name="mask.mp4"):
@@ -98,9 +107,16 @@ def temporal_smoothing_flow(video_path, output_dir, flow_threshold=0.5, alpha_fr
                           max_batch=R)
         worker.prime(first_frame)
 
+        yuv = _yuv_sink(out_overlay, width, height)
+
         def emit(i, outs, done, failing):
+            if yuv and done:   # the chunk's frames as I420 in one conversion call
+                i420 = N.bgr_to_i420(pipe.ins[i][:done], out_overlay.device)
             for t in range(done):
-                out_overlay.write(pipe.ins[i][t])
+                if yuv:
+                    out_overlay.write_yuv(i420[t])
+                else:
+                    out_overlay.write(pipe.ins[i][t])
                 out_mask.write(outs[0][t])
 
         pipe = ChunkPipeline(R, (height, width, 3), [(height, width)], cap.read, emit)
@@ -170,13 +186,18 @@ def compress_with_motion(input_video, mask_video, output_dir, quantization_level
 
             R = max(1, READ_AHEAD)
             mshape = tuple(frame_mask.shape)   # (H, W) or (H, W, 3) as decoded
-            comp = N.OFCompressor(width, height, float(quantization_level), max_batch=R, device=_device())
+            # a Y4M sink takes the compressor's I420 frames as they are (DVC_FLAG_OUT_I420)
+            yuv = _yuv_sink(out, width, height)
+            comp = N.OFCompressor(width, height, float(quantization_level), max_batch=R, device=_device(),
+                                  out_format="I420" if yuv else "BGR")
+            oshape = (height * 3 // 2, width) if yuv else (height, width, 3)
+            put = out.write_yuv if yuv else out.write
 
             def emit(i, outs, done, failing):
                 for t in range(done):
-                    out.write(outs[0][t])
+                    put(outs[0][t])
 
-            pipe = ChunkPipeline(R, [(height, width, 3), mshape], [(height, width, 3)], read_pair, emit)
+            pipe = ChunkPipeline(R, [(height, width, 3), mshape], [oshape], read_pair, emit)
             pipe.start()
             while True:
                 i, n = pipe.next_chunk()

@@ -53,11 +53,19 @@ class OFWorker(Worker):
     _outs = ("mask", "compressed")
 
     def __init__(self, width: int, height: int, *, device: int = 0, stream=None, device_ptrs: bool = False,
-                 keep_planes: bool = False, ktiming: bool = False, max_batch: int = 1, **kwargs):
+                 keep_planes: bool = False, ktiming: bool = False, max_batch: int = 1, out_format: str = "BGR",
+                 **kwargs):
+        """``out_format`` "BGR" or "I420": compressed frames as packed BGR, or
+        as the encoder's 4:2:0 input, (H*3/2, W) (DVC_FLAG_OUT_I420; W and H
+        even). The mask is the encoder's mono frame either way."""
+        if out_format not in ("BGR", "I420"):
+            raise ValueError(f"out_format {out_format!r}: BGR or I420")
+        self.out_format = out_format
         W, H = int(width), int(height)
-        self._oshape = (H, W, 3)
+        self._oshape = (H, W, 3) if out_format == "BGR" else (H * 3 // 2, W)
         self._astride = (W * H,)   # dvc_of_step_batch: mask_stride
-        self._open(derive_of_params(width, height, flags=0, **kwargs), kwargs.get("in_format", "BGR"), (W, H),
+        flags = N.DVC_FLAG_OUT_I420 if out_format == "I420" else 0
+        self._open(derive_of_params(width, height, flags=flags, **kwargs), kwargs.get("in_format", "BGR"), (W, H),
                    ((H, W), self._oshape), device=device, stream=stream, device_ptrs=device_ptrs,
                    keep_planes=keep_planes, ktiming=ktiming, max_batch=max_batch)
 
@@ -76,7 +84,8 @@ class OFWorker(Worker):
 
     def step(self, frame, mask=None, compressed=None, want=("mask", "compressed")):
         """of:70-101 + of:151-183 for one frame. Host mode returns ``(mask,
-        compressed)`` (H x W {0,255} and H x W x 3); device mode writes into the
+        compressed)`` (H x W {0,255} and H x W x 3, or the (H*3/2, W) I420
+        frame with ``out_format="I420"``); device mode writes into the
         given buffers and returns None."""
         return self._step(frame, mask, compressed, want)
 

@@ -99,7 +99,8 @@ class _SyntheticFrames:
 class Y4mReader:
     """cv2.VideoCapture-like reader of a YUV4MPEG2 file with 4:2:0 chroma
     (C420jpeg / C420 / C420paldv / C420mpeg2 / no C tag). Frames are memory-mapped;
-    ``pixel_format`` is "I420"."""
+    ``pixel_format`` is "I420". A Cmono file (what :class:`Y4mWriter` writes for a
+    mask video) opens with ``pixel_format`` "GRAY": ``read`` gives its (H, W) frames."""
 
     pixel_format = "I420"
 
@@ -126,10 +127,13 @@ class Y4mReader:
                 fps = int(num) / max(int(den), 1)
             elif k == b"C":
                 chroma = v
-        if W <= 0 or H <= 0 or W % 2 or H % 2 or not chroma.startswith(b"420"):
-            return   # 4:4:4 / 4:2:2 / mono sources are not 4:2:0 surfaces
+        mono = chroma == b"mono"
+        if W <= 0 or H <= 0 or not (mono or (W % 2 == 0 and H % 2 == 0 and chroma.startswith(b"420"))):
+            return   # 4:4:4 / 4:2:2 sources are not 4:2:0 surfaces
         self.W, self.H, self.fps = W, H, fps
-        self._frame_bytes = W * H * 3 // 2
+        if mono:
+            self.pixel_format = "GRAY"
+        self._frame_bytes = W * H if mono else W * H * 3 // 2
         raw = np.memmap(path, np.uint8, mode="r")
         off, frames = len(head), []
         while off < len(raw):   # FRAME[ params]\n + payload
@@ -157,13 +161,16 @@ class Y4mReader:
             return False, None
         o = self._offs[self._i]
         self._i += 1
-        return True, np.asarray(self._mm[o:o + self._frame_bytes]).reshape(self.H * 3 // 2, self.W)
+        return True, np.asarray(self._mm[o:o + self._frame_bytes]).reshape(self._frame_bytes // self.W, self.W)
 
     def read(self):
-        """(ok, BGR frame) as cv2.VideoCapture.read() gives it (cvtColor on the GPU)."""
+        """(ok, BGR frame) as cv2.VideoCapture.read() gives it (cvtColor on the GPU);
+        a Cmono file's single-channel frame as it is."""
         ok, f = self.read_yuv()
         if not ok:
             return False, None
+        if self.pixel_format == "GRAY":
+            return True, f
         from ._native import yuv420_to_bgr
         return True, yuv420_to_bgr(f, "I420", self.device)
 

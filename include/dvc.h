@@ -76,7 +76,14 @@ extern "C" {
                                      I420 frames of W*H*3/2 bytes (Y plane, then
                                      U and V planes of W/2 x H/2; out_stride >=
                                      W*H*3/2). block_size 4 or 8, W and H
-                                     multiples of it (else DVC_E_UNSUPPORTED)  */
+                                     multiples of it (else DVC_E_UNSUPPORTED).
+                                     OF (dvc_of_create, dvc_ofc_create): the
+                                     compressed frame of dvc_of_step, _step_batch
+                                     and dvc_ofc_run (of:185) in the same layout,
+                                     byte for byte dvc_bgr_to_i420 of the BGR
+                                     frame; the mask stays H*W bytes. W and H
+                                     even (else DVC_E_UNSUPPORTED at create);
+                                     partial 8x8 edge blocks stay legal        */
 
 #define DVC_FLAG_FD_UNFUSED  0x40u /* FD: write the outputs in one k_out pass after
                                      the accumulated mask instead of the fused
@@ -343,7 +350,8 @@ typedef struct dvc_of_params {
     int32_t iterations;
     int32_t poly_n;
     double poly_sigma;
-    uint32_t flags;      /* DVC_FLAG_DEVICE_PTRS | DVC_FLAG_KTIMING | DVC_FLAG_KEEP_PLANES */
+    uint32_t flags;      /* DVC_FLAG_DEVICE_PTRS | DVC_FLAG_KTIMING | DVC_FLAG_KEEP_PLANES |
+                            DVC_FLAG_OUT_I420 (compressed frames as I420, W and H even) */
     uint32_t max_batch;  /* 0/1..DVC_MAX_BATCH frames per device launch (see dvc_of_step_batch) */
     int32_t in_format;   /* DVC_FMT_BGR (0) / DVC_FMT_I420 / DVC_FMT_NV12 (of:66,145 read
                             BGR; 4:2:0 frames are converted on the GPU first) */
@@ -389,7 +397,8 @@ int dvc_of_set_state(dvc_of* h, const uint8_t* prev_gray, const uint8_t* raw_mas
  * motion-gated compression of the same frame with that mask (of:151-183).
  *   mask        nullable, H*W bytes {0,255}: the frame written to mask.mp4 (of:99)
  *   compressed  nullable, packed BGR rows of 3*W: the frame written to
- *               compressed.mp4 (of:185)
+ *               compressed.mp4 (of:185); with DVC_FLAG_OUT_I420 that frame as
+ *               I420, W*H*3/2 bytes
  * Synchronisation as dvc_fd_step. */
 int dvc_of_step(dvc_of* h, const uint8_t* bgr, size_t pitch, uint8_t* mask, uint8_t* compressed);
 
@@ -397,7 +406,8 @@ int dvc_of_step(dvc_of* h, const uint8_t* bgr, size_t pitch, uint8_t* mask, uint
  * Farneback iteration, the morphology and the compression run as grids over
  * tiles x frames; only the vote walks the frames in order. Results identical
  * to n dvc_of_step calls. Mask t at mask + t*mask_stride, compressed frame t at
- * compressed + t*out_stride. */
+ * compressed + t*out_stride (out_stride >= 3*W*H, or >= W*H*3/2 with
+ * DVC_FLAG_OUT_I420). */
 int dvc_of_step_batch(dvc_of* h, const uint8_t* bgr, size_t pitch, size_t frame_stride, int n,
                       uint8_t* mask, size_t mask_stride, uint8_t* compressed, size_t out_stride);
 
@@ -458,7 +468,10 @@ int dvc_of_compress(const uint8_t* bgr, size_t pitch, const uint8_t* mask, int w
  *   bgr + t*frame_stride      BGR rows of `pitch` (>= 3W)
  *   mask + t*mask_stride      mask rows of `mask_pitch`, mask_channels 1 (gray)
  *                             or 3 (BGR, as VideoCapture decodes mask.mp4)
- *   out + t*out_stride        compressed BGR rows of 3W (of:185)
+ *   out + t*out_stride        compressed BGR rows of 3W (of:185); with flags |=
+ *                             DVC_FLAG_OUT_I420 (W and H even, else
+ *                             DVC_E_UNSUPPORTED) that frame as I420, W*H*3/2
+ *                             bytes: dvc_bgr_to_i420 of it, byte for byte
  * Results identical to n dvc_of_compress calls (with the masks grayed).
  * quant = QTY_aggressive's constant (of:138, 100). Host pointers: synchronous
  * per call; DVC_FLAG_DEVICE_PTRS: device pointers, asynchronous on hip_stream
