@@ -29,6 +29,7 @@ DVC_FLAG_JOIN_STREAM = 0x8
 DVC_FLAG_OF_DIRECT_SUMS = 0x10
 DVC_FLAG_OUT_I420 = 0x20
 DVC_FLAG_FD_UNFUSED = 0x40
+DVC_FLAG_FD_KEPT_PLANE = 0x80
 KTIME_OUT, KTIME_FRONT_FUSED = 0, 1         # dvc_fd_ktime_kernel: which kernel KTIMING timed
 KTIME_FLOW, KTIME_FLOW_SCAN, KTIME_FLOW_SCAN2 = 2, 3, 4   # dvc_of_ktime_kernel: the level-0 flow kernel
 FMT_BGR, FMT_I420, FMT_NV12 = 0, 1, 2      # DVC_FMT_* frame formats (video I/O)

@@ -74,8 +74,8 @@ struct Slot {
     bool shared_ccl = false;  // and ev_ccl when its contour filter ran on the shared working set
     std::vector<FdGraph> graphs;   // the graph path's graphs of this slot's batches
     // the graph path's contour filter: the slot's own working set (S.c's
-    // mbits / kbits / kocc with its own run index, parents, areas, filled
-    // bits), so consecutive batches' filters overlap instead of queueing on
+    // mbits / kbits / kocc with its own run index, parents and areas), so
+    // consecutive batches' filters overlap instead of queueing on
     // one shared set; grown at the slot's graph batches (graph_ccl)
     dvc::CclBufs gc{};
     dvc_host::DevMem gc_mem;
@@ -436,8 +436,8 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
         h->slot[0].c.ptrs(ptrs0);
         // Only the motion bits (written by the front of a later batch while this
         // one's contour filter runs) and the kept bits (read by the accumulate
-        // stage after it) belong to a slot; the filter's run index, parents,
-        // areas and filled bits (~17 MB per 1080p frame) are touched only
+        // stage after it) belong to a slot; the filter's run index, parents
+        // and areas (~17 MB per 1080p frame) are touched only
         // inside the contour-filter stage, whose batches run one after another
         // on the handle's stream: one set serves all slots.
         for (int i = 0; i < dvc::CclBufs::NARR; ++i) {
@@ -526,7 +526,7 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
     {
         size_t sz[dvc::CclBufs::NARR];
         dvc::CclBufs::sizes(h->g, mb, sz);
-        if ((e = hipMemsetAsync(h->slot[0].c.gpar, 0, sz[6], h->stream)) != hipSuccess) return bad(e, "hipMemset");
+        if ((e = hipMemsetAsync(h->slot[0].c.gpar, 0, sz[dvc::CclBufs::I_GPAR], h->stream)) != hipSuccess) return bad(e, "hipMemset");
     }
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return bad(e, "hipStreamSynchronize");
     *out = h;
@@ -705,7 +705,7 @@ static int graph_ccl(dvc_fd* h, Slot& S, int n)
         }
     }
     // every frame slice's OUTSIDE gap node is its own root before any k_band (as at create)
-    HIP_OK(hipMemsetAsync(S.gc.gpar, 0, sz[6], graph_stream(h, (int)(&S - h->slot))));
+    HIP_OK(hipMemsetAsync(S.gc.gpar, 0, sz[dvc::CclBufs::I_GPAR], graph_stream(h, (int)(&S - h->slot))));
     S.gc_frames = cap;
     return DVC_OK;
 }
@@ -791,8 +791,11 @@ static int enqueue_graph(dvc_fd* h, Slot& S, std::vector<dvc::KNode> (&rec)[4], 
         for (int sg = 0; sg < 4; ++sg) {
             hipGraphNode_t nd = nullptr;
             // the accumulate stage waits for the previous batch's accumulate only
-            // before its last kernel (k_acc: the accumulated mask); k_dilate reads
-            // this batch's kept mask alone
+            // before its last kernel (k_acc: the accumulated mask); k_dilate, when
+            // the stage has it, reads this batch's kept mask alone. (The graph is
+            // one chain, so k_paint_dilate in the filter stage is behind the
+            // wait for the shared set and before the record of ev_ccl, and the
+            // slot's dblk / docc are free since S.ev_out, waited for at launch.)
             const size_t wat = sg == 2 && !rec[sg].empty() ? rec[sg].size() - 1 : 0;
             for (size_t u = 0; u <= rec[sg].size(); ++u) {
                 if (u == wat && waits[sg]) {
@@ -849,6 +852,13 @@ static int enqueue_graph(dvc_fd* h, Slot& S, std::vector<dvc::KNode> (&rec)[4], 
 // accumulated mask) are serial, each on its own stream. Batches of device
 // frames read in place take the graph path instead (enqueue_graph): the same
 // kernels, arguments and dependencies.
+// With the kept mask on chip (fuse_paint_dilate) the filter stage ends in
+// k_paint_dilate and the accumulate stage is k_acc alone. The events stay as
+// they are: ev_ccl, recorded after k_paint_dilate, still frees S.mbits and the
+// shared filter set (its last reads of rs, re, fpar, gE and area2 are that
+// kernel's, as they were k_paint's), and the filter stage's wait for acc(j)
+// now also keeps k_paint_dilate's dblk / docc stores behind k_acc(j), their
+// only reader.
 static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fstride, int n, uint8_t* ov, uint8_t* cp,
                          size_t ostride, int crows)
 {
@@ -1008,6 +1018,10 @@ static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fst
     a.err = h->err;
     a.frame0 = h->frames;
     h->last_fused = fused;
+    // the kept mask stays on chip: the filter stage ends in k_paint_dilate,
+    // which writes the slot's dblk / docc, and the accumulate stage is k_acc
+    // alone (DVC_FLAG_FD_KEPT_PLANE: k_paint -> kbits -> k_dilate instead)
+    const bool onchip = !(h->p.flags & DVC_FLAG_FD_KEPT_PLANE) && dvc::fuse_paint_dilate(S.c, a);
     if (graph) {
         std::vector<dvc::KNode> rec[4];
         hipError_t e[4];
@@ -1021,9 +1035,9 @@ static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fst
         e[0] = dvc::launch_front(d, dp, dfs, sf, n, h->gray[h->gcur], h->gray[h->gcur ^ 1], h->gs, S.c.mbits, h->g,
                                  h->p.ithresh, z, fused ? &fo : nullptr);
         dvc::g_krec = &rec[1];
-        e[1] = dvc::launch_ccl(shared ? S.c : S.gc, h->g, n, h->p.min_area2, z);
+        e[1] = dvc::launch_ccl(shared ? S.c : S.gc, h->g, n, h->p.min_area2, z, onchip ? &a : nullptr);
         dvc::g_krec = &rec[2];
-        e[2] = dvc::launch_accumulate(a, z);
+        e[2] = dvc::launch_accumulate(a, z, onchip);
         dvc::g_krec = &rec[3];
         e[3] = dvc::launch_out(a, z, fused);
         dvc::g_krec = nullptr;
@@ -1054,11 +1068,11 @@ static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fst
         HIP_OK(hipEventRecord(S.ev_front, h->s_front));
         HIP_OK(hipStreamWaitEvent(s_ccl, S.ev_front, 0));
         if (S.recorded) HIP_OK(hipStreamWaitEvent(s_ccl, S.ev_acc, 0));
-        if (!(skip & 2)) HIP_OK(dvc::launch_ccl(S.c, h->g, n, h->p.min_area2, s_ccl));
+        if (!(skip & 2)) HIP_OK(dvc::launch_ccl(S.c, h->g, n, h->p.min_area2, s_ccl, onchip ? &a : nullptr));
         HIP_OK(hipEventRecord(S.ev_ccl, s_ccl));
         HIP_OK(hipStreamWaitEvent(h->s_acc, S.ev_ccl, 0));
         if (S.recorded) HIP_OK(hipStreamWaitEvent(h->s_acc, S.ev_out, 0));
-        if (!(skip & 4)) HIP_OK(dvc::launch_accumulate(a, h->s_acc));
+        if (!(skip & 4)) HIP_OK(dvc::launch_accumulate(a, h->s_acc, onchip));
         HIP_OK(hipEventRecord(S.ev_acc, h->s_acc));
         HIP_OK(hipStreamWaitEvent(h->s_out, S.ev_acc, 0));
         if (timed && !fused) HIP_OK(hipEventRecord(h->ev[h->ev_used], h->s_out));
@@ -1328,7 +1342,7 @@ int dvc_contour_filter(const uint8_t* mask, int width, int height, int64_t min_a
     hipStream_t s = nullptr;
     e = hipMemcpy(c.mbits, bits.data(), 8 * H * WW, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(stats, 0, 8 * 4 * 64);
-    if (e == hipSuccess) e = hipMemset(c.gpar, 0, sz[6]);
+    if (e == hipSuccess) e = hipMemset(c.gpar, 0, sz[dvc::CclBufs::I_GPAR]);
     if (e == hipSuccess) e = dvc::launch_ccl(c, g, 1, min_area2, s);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     unsigned long long st[4];

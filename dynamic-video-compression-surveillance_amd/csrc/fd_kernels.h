@@ -35,13 +35,12 @@ struct alignas(8) DctMat {
 // slice of each array (sizes per frame below, see frame()).
 struct CclBufs {
     uint64_t* mbits;        // H x WW motion mask
-    uint64_t* fbits;        // H x WW filled mask (not-E)
     uint16_t *rs, *re;      // H x CAP run starts / ends
     uint32_t* nfg;          // H runs per row
     uint32_t* fpar;         // H x CAP run union-find parents (root after k_area)
     uint32_t* gpar;         // 1 + H x (CAP+1) gap parents, node 0 = outside
     uint8_t* gE;            // H x (CAP+1) gap is outside (1) / hole (0)
-    uint32_t* area2;        // H x CAP 2*area per root
+    uint32_t* area2;        // H x CAP 2*area per root (k_resolve -> k_area: every run's own term)
     uint64_t* kbits;        // H x WW kept (filtered) mask
     unsigned long long* stats;  // 64 slots x 4 counters (shared by all frames)
     // Sparse masks (a surveillance frame is mostly still): nullable H bytes per
@@ -61,30 +60,31 @@ struct CclBufs {
     __host__ __device__ CclBufs frame(size_t f, const RowGeom& g) const
     {
         const size_t nb = (size_t)g.H * g.WW, nr = (size_t)g.H * g.CAP, ng = (size_t)g.H * (g.CAP + 1);
-        return CclBufs{mbits + f * nb, fbits + f * nb, rs + f * nr, re + f * nr, nfg + f * g.H, fpar + f * nr,
+        return CclBufs{mbits + f * nb, rs + f * nr, re + f * nr, nfg + f * g.H, fpar + f * nr,
                        gpar + f * (ng + 1), gE + f * ng, area2 + f * nr, kbits + f * nb, stats,
                        kocc ? kocc + f * g.H : nullptr, kfull, rowb + f * 2 * g.H};
     }
     // Bytes of every array for `frames` frames (host allocation), in the order
     // of ptrs(): a caller that allocates these NARR arrays has every buffer the
     // kernels touch (launch_ccl refuses a CclBufs without rowb).
-    static constexpr int NARR = 11;
+    static constexpr int NARR = 10;
+    static constexpr int I_GPAR = 5;   // gpar's index below (its OUTSIDE nodes are zeroed before the first launch)
     static void sizes(const RowGeom& g, size_t frames, size_t out[NARR])
     {
         const size_t nb = (size_t)g.H * g.WW, nr = (size_t)g.H * g.CAP, ng = (size_t)g.H * (g.CAP + 1);
-        const size_t s[NARR] = {8 * nb, 8 * nb, 2 * nr, 2 * nr, 4 * (size_t)g.H, 4 * nr, 4 * (ng + 1), ng, 4 * nr, 8 * nb,
+        const size_t s[NARR] = {8 * nb, 2 * nr, 2 * nr, 4 * (size_t)g.H, 4 * nr, 4 * (ng + 1), ng, 4 * nr, 8 * nb,
                                 rowb_bytes(g, 1)};
         for (int i = 0; i < NARR; ++i) out[i] = s[i] * frames;
     }
-    // the arrays sizes() describes; indices 1..8 and 10 are contour-filter
-    // working set (touched only inside launch_ccl), 0 and 9 its input / output
+    // the arrays sizes() describes; indices 1..7 and 9 are contour-filter
+    // working set (touched only inside launch_ccl), 0 and 8 its input / output
     void ptrs(void** out[NARR])
     {
-        void** p[NARR] = {(void**)&mbits, (void**)&fbits, (void**)&rs,    (void**)&re,    (void**)&nfg, (void**)&fpar,
+        void** p[NARR] = {(void**)&mbits, (void**)&rs,    (void**)&re,    (void**)&nfg,   (void**)&fpar,
                           (void**)&gpar,  (void**)&gE,    (void**)&area2, (void**)&kbits, (void**)&rowb};
         for (int i = 0; i < NARR; ++i) out[i] = p[i];
     }
-    static bool working_set(int i) { return (i >= 1 && i <= 8) || i == 10; }
+    static bool working_set(int i) { return (i >= 1 && i <= 7) || i == 9; }
 };
 
 // The frames k_front / k_out / k_out_gen read: packed BGR rows (fmt 0,
@@ -125,7 +125,7 @@ struct BackArgs {
     const uint8_t* kocc;    // nullable: kept row has bits, H per frame (CclBufs::kocc); rows without are not read
     uint8_t* docc;          // fast layout with kocc: block row by of frame t has dilated bits, docc[by * n + t]
     // fast layout
-    void* dblk;             // dilated mask, block-major BxB bit fields per frame (k_dilate -> k_acc)
+    void* dblk;             // dilated mask, block-major BxB bit fields per frame (k_paint_dilate / k_dilate -> k_acc)
     void* rblk;             // acc > 127 per pixel, block-major BxB bit fields per frame (k_acc -> k_out)
     uint64_t* sbits;        // acc all zero per block, NBY x SW per frame (k_acc -> k_out)
     int SW;                 // 64-block words per block row = ceil(NBX/64)
@@ -195,9 +195,17 @@ hipError_t launch_resize(const uint8_t* src, int spitch, size_t sstride, uint8_t
                          int n, const ResizeTab& t, hipStream_t s);
 int band_rows(const RowGeom& g);
 size_t ccl_max_lds(const RowGeom& g);   // dvc_fd_create refuses frames wider than the LDS allows
-hipError_t launch_ccl(const CclBufs& c, const RowGeom& g, int n, int64_t min_area2, hipStream_t s);
-// k_dilate then k_acc (the accumulated-mask recurrence: batches in order)
-hipError_t launch_accumulate(const BackArgs& a, hipStream_t s);
+// The kept mask can stay on chip: k_paint_dilate (painting and dilation in one
+// kernel, the kept rows in LDS) instead of k_paint -> kbits / kocc -> k_dilate.
+bool fuse_paint_dilate(const CclBufs& c, const BackArgs& a);
+// back (only where fuse_paint_dilate holds): the contour filter ends in
+// k_paint_dilate, which writes back->dblk / docc and leaves c.kbits / kocc
+// alone; launch_accumulate then runs with dilated = true.
+hipError_t launch_ccl(const CclBufs& c, const RowGeom& g, int n, int64_t min_area2, hipStream_t s,
+                      const BackArgs* back = nullptr);
+// k_dilate (unless the filter stage already dilated) then k_acc (the
+// accumulated-mask recurrence: batches in order)
+hipError_t launch_accumulate(const BackArgs& a, hipStream_t s, bool dilated = false);
 // k_acc's short form computes fmaf(acc, alpha, D) with D = +0 or fmaf(255, beta,
 // gamma) and drops the [0, 255] clamp. Exact when fmaf(0, beta, gamma) is +0
 // (the dilated-0 addend; D is then a sign-mask AND of the dil-1 bits) and the

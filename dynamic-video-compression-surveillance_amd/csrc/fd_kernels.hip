@@ -11,12 +11,15 @@
 //             joined to the OUTSIDE node) -> band-local roots as global ids
 //   k_merge   per band seam: global unions of band roots (atomicMin links)
 //   k_resolve gaps reaching node 0 are outside (E); the rest are holes: hole
-//             pixels are painted into the filled mask F = not E, and the runs
-//             left/right of a hole are united (nested components join the
-//             external component that encloses them)
-//   k_area    2*contourArea of every external component from F's 2x2 windows,
-//             accumulated per root (fd:100-103)
-//   k_paint   kept components -> filtered bit mask (drawContours FILLED, fd:104)
+//             pixels are painted into the filled mask F = not E (rows in LDS
+//             only), and the runs left/right of a hole are united (nested
+//             components join the external component that encloses them);
+//             every run's share of 2*contourArea from F's 2x2 windows
+//   k_area    those shares accumulated per root: 2*contourArea of every
+//             external component (fd:100-103)
+//   k_paint   kept components -> filtered bit mask (drawContours FILLED, fd:104);
+//             block sizes 4 and 8: k_paint_dilate, the mask painted into LDS
+//             and dilated from there (fd:106) in the same kernel
 //   k_back    7x7 dilate (fd:106), addWeighted (fd:107), red overlay
 //             (fd:110-111), static BxB block DCT quantisation + YCrCb round trip
 //             (fd:115-130)
@@ -930,7 +933,8 @@ __global__ void __launch_bounds__(256) k_merge(CclBufs cb, RowGeom g, int BH)
 // CG lanes — CG = 16: 4 rows per wave, 16 per workgroup; CG = 8 (batches of
 // >= 64 frames, launch_ccl): 8 rows per wave, 32 per workgroup — so one wave
 // carries several independent global-memory dependency chains (the union-find
-// walks); a row's runs are strided over its CG lanes. LDS: one mask row per group.
+// walks); a row's runs are strided over its CG lanes. LDS: one mask row per
+// group (k_resolve: and one halo row a workgroup; k_area: none).
 template <int CG> constexpr int cg_rows() { return 4 * (64 / CG); }
 
 template <int CG>
@@ -996,9 +1000,21 @@ __global__ void __launch_bounds__(256) k_paint(CclBufs cb, RowGeom g, int64_t mi
 // Gaps whose root is OUTSIDE are E; the rest are holes: painted into the
 // filled row F = not E, and the runs either side of a hole united (the
 // component inside a hole of another joins the external one enclosing it).
+//
+// The filled rows never leave LDS: the workgroup holds the F rows of its
+// cg_rows consecutive image rows, one slice per lane group, and row y+1 of a
+// row is the next group's slice after one workgroup barrier. Row y+1 of the
+// workgroup's last row is a halo: its gaps are resolved again here into a
+// spare slice (finds and paints only: its unions and its gE belong to the
+// workgroup that owns the row). With F' = F row y+1, a run [s, e] of row y
+// then contributes to 2*contourArea of its component
+//   2*popc(F'[s..e]) - F'(s) - F'(e) + [F'(s-1)&F'(s)] + [F'(e)&F'(e+1)]
+// per filled run, split additively over the runs and holes of the filled run;
+// the term is left in the run's own area2 slot (zero after k_band) for k_area.
 template <int CG>
 __global__ void __launch_bounds__(256) k_resolve(CclBufs cb, RowGeom g)
 {
+    constexpr int ROWS = cg_rows<CG>();
     const CclBufs fb = cb.frame(blockIdx.y, g);
     const uint16_t* __restrict__ rs = fb.rs;
     const uint16_t* __restrict__ re = fb.re;
@@ -1007,77 +1023,97 @@ __global__ void __launch_bounds__(256) k_resolve(CclBufs cb, RowGeom g)
     uint32_t* gpar = fb.gpar;
     uint8_t* __restrict__ gE = fb.gE;
     const uint64_t* __restrict__ mbits = fb.mbits;
-    uint64_t* __restrict__ fbits = fb.fbits;
-    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_r[];
+    uint32_t* __restrict__ area2 = fb.area2;
+    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_r[];   // ROWS + 1 slices of WW words
+    const int WW = g.WW;
     const int slot = threadIdx.x / CG, sl = threadIdx.x & (CG - 1);
-    const int y = blockIdx.x * cg_rows<CG>() + slot;
+    const int y = blockIdx.x * ROWS + slot, yh = (blockIdx.x + 1) * ROWS;
     const bool act = y < g.H;
-    unsigned long long* s_f = lds_r + (size_t)slot * g.WW;
+    unsigned long long* s_f = lds_r + (size_t)slot * WW;
+    unsigned long long* s_h = lds_r + (size_t)ROWS * WW;
     // a row without runs is one gap touching both image borders: outside (E),
-    // its filled row is zero — k_area knows that from nfg and never reads it
+    // its filled row is zero
     const int n = act ? (int)nfg[y] : 0;
-    if (n)
-        for (int w = sl; w < g.WW; w += CG) s_f[w] = mbits[(size_t)y * g.WW + w];
-    wave_sync_lds();
+    const int nh = yh < g.H ? (int)nfg[yh] : 0;
+    for (int w = sl; w < WW; w += CG) s_f[w] = n ? mbits[(size_t)y * WW + w] : 0ull;
+    for (int w = threadIdx.x; w < WW; w += 256) s_h[w] = nh ? mbits[(size_t)yh * WW + w] : 0ull;
+    __syncthreads();
     // (no runs: the row's one gap is the border gap k_band already tied to
     // OUTSIDE, and no kernel reads its gE)
-    if (n) {
-        const uint32_t base = fb.rowb[2 * y], gbase = fb.rowb[2 * y + 1];
-        for (int k = sl; k <= n; k += CG) {
-            const int a = k == 0 ? 0 : (int)re[base + k - 1] + 1;
-            const int b = k == n ? g.W - 1 : (int)rs[base + k] - 1;
-            uint8_t e = 1;
-            if (a <= b) {
-                const uint32_t r = uf_find(gpar, gbase + k);
-                atomicMin(gpar + gbase + k, r);
-                e = r == 0;
-                if (!e) {  // a hole: interior gap, both neighbours are runs of this row
-                    uf_union(fpar, base + k - 1, base + k);
-                    paint_bits(s_f, 0, g.WW, a, b);
-                }
+    const uint32_t base = n ? fb.rowb[2 * y] : 0u, gbase = n ? fb.rowb[2 * y + 1] : 0u;
+    const uint32_t hbase = nh ? fb.rowb[2 * yh] : 0u, hgbase = nh ? fb.rowb[2 * yh + 1] : 0u;
+    // One loop over a lane's gaps of its own row (k = sl, sl + CG, ..) and then
+    // of the halo row, whose gaps are dealt from the workgroup's last lane
+    // down: lanes with few gaps of their own resolve the halo's while the
+    // others walk theirs, in the same iterations.
+    const int hl = 255 - (int)threadIdx.x;
+    const int nown = n && sl <= n ? (n - sl) / CG + 1 : 0;
+    const int nhalo = nh && hl <= nh ? (nh - hl) / 256 + 1 : 0;
+    for (int it = 0; it < nown + nhalo; ++it) {
+        const bool halo = it >= nown;
+        const int k = halo ? hl + (it - nown) * 256 : sl + it * CG;
+        const int nn = halo ? nh : n;
+        const uint32_t bs = halo ? hbase : base, gb = halo ? hgbase : gbase;
+        const int a = k == 0 ? 0 : (int)re[bs + k - 1] + 1;
+        const int b = k == nn ? g.W - 1 : (int)rs[bs + k] - 1;
+        uint8_t e = 1;
+        if (a <= b) {
+            const uint32_t r = uf_find(gpar, gb + k);
+            if (!halo) atomicMin(gpar + gb + k, r);
+            e = r == 0;
+            if (!e) {  // a hole: interior gap, both neighbours are runs of this row
+                if (!halo) uf_union(fpar, bs + k - 1, bs + k);
+                paint_bits(halo ? s_h : s_f, 0, WW, a, b);
             }
-            gE[gbase - 1 + k] = e;
         }
+        if (!halo) gE[gb - 1 + k] = e;
     }
-    wave_sync_lds();
-    if (n)
-        for (int w = sl; w < g.WW; w += CG) fbits[(size_t)y * g.WW + w] = s_f[w];
+    __syncthreads();
+    if (!n || y == g.H - 1) return;   // the last row has no row below: its terms stay 0
+    // an interior gap is a hole exactly when its pixels are set in the row's own F
+    const uint64_t* f = reinterpret_cast<const uint64_t*>(s_f);
+    const uint64_t* b = reinterpret_cast<const uint64_t*>(slot + 1 < ROWS ? s_f + WW : s_h);
+    for (int k = sl; k < n; k += CG) {
+        const uint32_t id = base + k;
+        const int s = rs[id], e = re[id];
+        const bool hole_l = k > 0 && bit_at(f, s - 1), hole_r = k < n - 1 && bit_at(f, e + 1);
+        int c = 2 * popc_range(b, s, e);
+        if (!hole_l) {
+            int bs = bit_at(b, s);
+            c -= bs;
+            if (s >= 1 && bs && bit_at(b, s - 1)) c += 1;
+        }
+        if (!hole_r) {
+            int be = bit_at(b, e);
+            c -= be;
+            if (e <= g.W - 2 && be && bit_at(b, e + 1)) c += 1;
+        }
+        if (hole_r) c += 2 * popc_range(b, e + 1, (int)rs[id + 1] - 1);
+        area2[id] = (uint32_t)c;
+    }
 }
 
 // ------------------------------------------------------------------- area ---
-// Row y with F row y+1 staged in LDS. 2*area per filled run:
-//   2*popc(F'[s..e]) - F'(s) - F'(e) + [F'(s-1)&F'(s)] + [F'(e)&F'(e+1)]
-// (F' = row y+1), split additively over the runs and holes of the filled run.
+// 2*contourArea per component: every run's term (k_resolve, in the run's own
+// area2 slot) summed into its root's slot. A root's own term is already there,
+// and only roots are ever added to, so a run that is no root reads its plain
+// term. No LDS.
 template <int CG>
 __global__ void __launch_bounds__(256) k_area(CclBufs cb, RowGeom g)
 {
     const CclBufs fb = cb.frame(blockIdx.y, g);
-    const uint16_t* __restrict__ rs = fb.rs;
-    const uint16_t* __restrict__ re = fb.re;
     const uint32_t* __restrict__ nfg = fb.nfg;
     uint32_t* fpar = fb.fpar;
-    const uint8_t* __restrict__ gE = fb.gE;
-    const uint64_t* __restrict__ fbits = fb.fbits;
-    uint32_t* __restrict__ area2 = fb.area2;
+    uint32_t* area2 = fb.area2;
     unsigned long long* __restrict__ stats = fb.stats;
-    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_b[];
     const int lane = threadIdx.x & 63;
     const int slot = threadIdx.x / CG, sl = threadIdx.x & (CG - 1), g0 = lane & ~(CG - 1);
     const int y = blockIdx.x * cg_rows<CG>() + slot;
     const bool act = y < g.H;
-    unsigned long long* s_b = lds_b + (size_t)slot * g.WW;
-    const bool last = y == g.H - 1;
     const int n = act ? (int)nfg[y] : 0;
-    // F row y+1 (k_resolve): zero when row y+1 has no runs, not needed when row y has none
-    const bool fnext = n && !last && nfg[y + 1];
-    if (n)
-        for (int w = sl; w < g.WW; w += CG) s_b[w] = fnext ? fbits[(size_t)(y + 1) * g.WW + w] : 0ull;
-    wave_sync_lds();
     int comps = 0;
-    if (act) {
+    if (n) {
         const uint32_t base = fb.rowb[2 * y];
-        const uint8_t* ge = gE + (fb.rowb[2 * y + 1] - 1);
-        const uint64_t* b = reinterpret_cast<const uint64_t*>(s_b);
         const unsigned long long gmask = ((1ull << CG) - 1ull) << g0;
         for (int k0 = 0; k0 < n; k0 += CG) {   // uniform trip count within the group: it reduces below
             const int k = k0 + sl;
@@ -1089,21 +1125,7 @@ __global__ void __launch_bounds__(256) k_area(CclBufs cb, RowGeom g)
                 r = uf_find(fpar, id);
                 atomicMin(fpar + id, r);
                 comps += r == id;
-            }
-            if (valid && !last) {
-                int s = rs[id], e = re[id];
-                c = 2 * popc_range(b, s, e);
-                if (k == 0 || ge[k]) {
-                    int bs = bit_at(b, s);
-                    c -= bs;
-                    if (s >= 1 && bs && bit_at(b, s - 1)) c += 1;
-                }
-                if (k == n - 1 || ge[k + 1]) {
-                    int be = bit_at(b, e);
-                    c -= be;
-                    if (e <= g.W - 2 && be && bit_at(b, e + 1)) c += 1;
-                }
-                if (k + 1 < n && !ge[k + 1]) c += 2 * popc_range(b, e + 1, (int)rs[id + 1] - 1);
+                if (r != id) c = (int)area2[id];
             }
             // one atomic per run of lanes with the same root (a large component's
             // runs of a row would otherwise all hit one address)
@@ -1240,6 +1262,124 @@ __global__ void __launch_bounds__(256) k_dilate(BackArgs a)
 #pragma unroll
         for (int i = 0; i < B; ++i) f |= ((out[i] >> (B * b)) & ((1ull << B) - 1)) << (B * i);
         if (b < nb) *reinterpret_cast<BT*>(db + (dbo + (uint32_t)(b * sizeof(BT)))) = (BT)f;
+    }
+}
+
+// k_paint and k_dilate in one kernel, the kept mask in LDS only (fuse_paint_dilate
+// below says when). A workgroup owns PD_ROWS = 32 pixel rows of frame blockIdx.y
+// (8 block rows of B = 4, 4 of B = 8): it paints the kept rows its windows need
+// — its own and `anchor` above, k - 1 - anchor below, the halo rows again in
+// every workgroup that needs them, rows outside the image left empty — a row a
+// lane group as k_paint does, and after one barrier dilates them from LDS, one
+// lane per (64-px word column, block row) as k_dilate does, into the same dblk
+// and docc: a block row whose window holds no kept bit writes only docc = 0.
+// LDS: 31 + k rows of WW words and a "row has bits" flag each (9 KB at 1080p).
+constexpr int PD_ROWS = 32;
+__host__ __device__ constexpr size_t paint_dilate_lds(int WW, int k) { return (size_t)(PD_ROWS + k - 1) * (8 * WW + 4); }
+
+template <int B, int CG>
+__global__ void __launch_bounds__(256) k_paint_dilate(CclBufs cb, BackArgs a, int64_t min_area2)
+{
+    typedef typename BlkT<B>::T BT;
+    constexpr int BRG = PD_ROWS / B, PER = 64 / B;
+    const RowGeom g = a.g;
+    const int W = g.W, H = g.H, WW = g.WW, NBX = a.NBX, NBY = a.NBY, t = blockIdx.y;
+    const int k = a.ksize, an = a.anchor, R = B + k - 1, NR = PD_ROWS + k - 1;
+    const CclBufs fb = cb.frame(t, g);
+    const uint16_t* __restrict__ rs = fb.rs;
+    const uint16_t* __restrict__ re = fb.re;
+    const uint32_t* __restrict__ nfg = fb.nfg;
+    const uint32_t* __restrict__ fpar = fb.fpar;
+    const uint8_t* __restrict__ gE = fb.gE;
+    const uint32_t* __restrict__ area2 = fb.area2;
+    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_pd[];
+    unsigned long long* s_k = lds_pd;                                             // LDS row lr = image row ytop + lr
+    uint32_t* s_any = reinterpret_cast<uint32_t*>(lds_pd + (size_t)NR * WW);
+    const int ytop = blockIdx.x * PD_ROWS - an;
+    for (int i = threadIdx.x; i < NR * WW; i += 256) s_k[i] = 0ull;
+    for (int i = threadIdx.x; i < NR; i += 256) s_any[i] = 0u;
+    __syncthreads();
+    // ---- paint (k_paint): every run of a kept component and the holes between its runs
+    const int slot = threadIdx.x / CG, sl = threadIdx.x & (CG - 1);
+    for (int lr = slot; lr < NR; lr += 256 / CG) {
+        const int y = ytop + lr;
+        if (y < 0 || y >= H) continue;
+        const int n = (int)nfg[y];
+        if (!n) continue;
+        const uint32_t base = fb.rowb[2 * y];
+        const uint8_t* ge = gE + (fb.rowb[2 * y + 1] - 1);   // gap node g at gE[g - 1]
+        unsigned long long* row = s_k + (size_t)lr * WW;
+        for (int i = sl; i < n; i += CG) {
+            const uint32_t root = fpar[base + i];
+            if (!((int64_t)area2[root] > min_area2)) continue;  // contourArea > min_area
+            const int e = re[base + i];
+            paint_bits(row, 0, WW, rs[base + i], e);
+            if (i + 1 < n && !ge[i + 1]) paint_bits(row, 0, WW, e + 1, (int)rs[base + i + 1] - 1);
+            s_any[lr] = 1u;
+        }
+    }
+    __syncthreads();
+    // ---- dilate (k_dilate): out bit x = OR of the window rows' bits x - anchor .. x + k - 1 - anchor
+    const uint64_t* kb = reinterpret_cast<const uint64_t*>(s_k);
+    uint8_t* db = reinterpret_cast<uint8_t*>(a.dblk) + (size_t)t * NBY * NBX * sizeof(BT);
+    for (int idx = threadIdx.x; idx < WW * BRG; idx += 256) {
+        const int wi = idx % WW, byl = idx / WW, by = blockIdx.x * BRG + byl;
+        if (by >= NBY) break;
+        const int lr0 = byl * B;    // the window of block row by: LDS rows lr0 .. lr0 + R - 1
+        uint32_t any = 0;
+        for (int r = 0; r < R; ++r) any |= s_any[lr0 + r];
+        if (wi == 0) a.docc[(size_t)by * a.n + t] = (uint8_t)(any != 0);
+        if (!any) continue;
+        // pixels past W (the last word) are not pixels: their dilated bits stay 0
+        const uint64_t vmask = (wi == WW - 1 && (W & 63)) ? (1ull << (W & 63)) - 1ull : ~0ull;
+        uint64_t out[B];
+#pragma unroll
+        for (int i = 0; i < B; ++i) out[i] = 0;
+        for (int r = 0; r < R; ++r) {
+            if (!s_any[lr0 + r]) continue;
+            const uint64_t* row = kb + (size_t)(lr0 + r) * WW;
+            const uint64_t c = row[wi], pv = wi > 0 ? row[wi - 1] : 0ull, nv = wi + 1 < WW ? row[wi + 1] : 0ull;
+            uint64_t o = c;
+            for (int off = 1; off <= k - 1 - an; ++off) o |= (c >> off) | (nv << (64 - off));
+            for (int off = 1; off <= an; ++off) o |= (c << off) | (pv >> (64 - off));
+            o &= vmask;
+#pragma unroll
+            for (int i = 0; i < B; ++i)
+                if (r - i >= 0 && r - i < k) out[i] |= o;
+        }
+#pragma unroll
+        for (int i = 0; i < B; ++i)   // rows past H (a partial last block row) are not pixels
+            if (by * B + i >= H) out[i] = 0;
+        // the word's 64 / B block fields are contiguous: 32 B (B = 4) or 64 B (B = 8),
+        // stored 16 bytes at a time; field by field only in the last, partial
+        // word of a row and where the row's fields do not start on 16 bytes
+        BT f[PER];
+#pragma unroll
+        for (int b = 0; b < PER; ++b) {
+            uint64_t v = 0;
+#pragma unroll
+            for (int i = 0; i < B; ++i) v |= ((out[i] >> (B * b)) & ((1ull << B) - 1)) << (B * i);
+            f[b] = (BT)v;
+        }
+        const int nb = min(PER, NBX - wi * PER);
+        uint8_t* dst = db + (size_t)(by * NBX + wi * PER) * sizeof(BT);
+        if (nb == PER && !(reinterpret_cast<uintptr_t>(dst) & 15)) {
+            constexpr int Q = 16 / (int)sizeof(BT);   // fields a 16-byte store
+#pragma unroll
+            for (int q = 0; q < PER / Q; ++q) {
+                uint32_t d[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (B == 4) d[j] = (uint32_t)f[q * Q + 2 * j] | ((uint32_t)f[q * Q + 2 * j + 1] << 16);
+                    else d[j] = (uint32_t)((uint64_t)f[q * Q + (j >> 1)] >> (32 * (j & 1)));
+                }
+                *reinterpret_cast<uint4*>(dst + 16 * q) = make_uint4(d[0], d[1], d[2], d[3]);
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < PER; ++b)
+                if (b < nb) reinterpret_cast<BT*>(dst)[b] = f[b];
+        }
     }
 }
 
@@ -2177,7 +2317,7 @@ int band_rows(const RowGeom&) { return BAND_ROWS; }
 size_t ccl_max_lds(const RowGeom& g)
 {
     return std::max({band_lds(g, BAND_ROWS, 1024), (size_t)8 * merge_lds_words(g.WW) * (256 / MG),
-                     (size_t)8 * g.WW * cg_rows<8>()});
+                     (size_t)8 * g.WW * (cg_rows<8>() + 1)});
 }
 
 // Node budget of a band: 1024 (4 KB of parents beside the run index, ~14 KB
@@ -2193,14 +2333,41 @@ static int band_budget(const RowGeom& g)
     return (int)std::max<long long>(1024, rest / 4);
 }
 
-hipError_t launch_ccl(const CclBufs& c, const RowGeom& g, int n, int64_t min_area2, hipStream_t s)
+// DVC_CCL_SUB=F (experiment): the five kernels over sub-batches of F frames
+static int ccl_sub()
 {
-    if (!c.rowb) return hipErrorInvalidValue;   // every kernel below finds its nodes through rowb
-    // DVC_CCL_SUB=F (experiment): the five kernels over sub-batches of F frames
     static const int sub = [] {
         const char* e = dvc::tune_env("DVC_CCL_SUB");
         return e ? atoi(e) : 0;
     }();
+    return sub;
+}
+
+// The kept mask stays on chip (k_paint_dilate) for the block-major back end
+// when the dilation window of a block row fits k_dilate's row mask (B + k - 1
+// <= 64 rows) and the workgroup's 31 + k rows fit 32 KB of LDS (k = 7: frames
+// up to 6848 px wide; k = 61: up to 2816 px); not when the kept or the dilated
+// plane is read back (KEEP_PLANES), which needs the planes.
+bool fuse_paint_dilate(const CclBufs& c, const BackArgs& a)
+{
+    return fast_block(a.B) && a.B + a.ksize - 1 <= 64 && paint_dilate_lds(a.g.WW, a.ksize) <= 32768 && a.kocc &&
+           a.docc && !c.kfull && !a.dbg_dil && ccl_sub() <= 0;
+}
+
+template <int CG>
+static void launch_paint_dilate(const CclBufs& c, const BackArgs& a, int64_t min_area2, hipStream_t s)
+{
+    const dim3 grid((a.NBY * a.B + PD_ROWS - 1) / PD_ROWS, a.n);
+    const size_t lds = paint_dilate_lds(a.g.WW, a.ksize);
+    if (a.B == 4) klaunch((k_paint_dilate<4, CG>), grid, dim3(256), lds, s, c, a, min_area2);
+    else klaunch((k_paint_dilate<8, CG>), grid, dim3(256), lds, s, c, a, min_area2);
+}
+
+hipError_t launch_ccl(const CclBufs& c, const RowGeom& g, int n, int64_t min_area2, hipStream_t s, const BackArgs* back)
+{
+    if (!c.rowb) return hipErrorInvalidValue;   // every kernel below finds its nodes through rowb
+    if (back && (!fuse_paint_dilate(c, *back) || back->n != n)) return hipErrorInvalidValue;
+    const int sub = ccl_sub();
     if (sub > 0 && n > sub) {
         for (int f0 = 0; f0 < n; f0 += sub) {
             const hipError_t e = launch_ccl(c.frame(f0, g), g, std::min(sub, n - f0), min_area2, s);
@@ -2222,23 +2389,25 @@ hipError_t launch_ccl(const CclBufs& c, const RowGeom& g, int n, int64_t min_are
     if (cg == 8) {
         const int grows = (g.H + cg_rows<8>() - 1) / cg_rows<8>();
         const size_t glds = (size_t)8 * g.WW * cg_rows<8>();
-        klaunch(k_resolve<8>, dim3(grows, n), dim3(256), glds, s, c, g);
-        klaunch(k_area<8>, dim3(grows, n), dim3(256), glds, s, c, g);
-        klaunch(k_paint<8>, dim3(grows, n), dim3(256), glds, s, c, g, min_area2);
+        klaunch(k_resolve<8>, dim3(grows, n), dim3(256), glds + 8 * g.WW, s, c, g);   // + the halo row
+        klaunch(k_area<8>, dim3(grows, n), dim3(256), 0, s, c, g);
+        if (back) launch_paint_dilate<8>(c, *back, min_area2, s);
+        else klaunch(k_paint<8>, dim3(grows, n), dim3(256), glds, s, c, g, min_area2);
     } else {
         const int grows = (g.H + cg_rows<16>() - 1) / cg_rows<16>();
         const size_t glds = (size_t)8 * g.WW * cg_rows<16>();
-        klaunch(k_resolve<16>, dim3(grows, n), dim3(256), glds, s, c, g);
-        klaunch(k_area<16>, dim3(grows, n), dim3(256), glds, s, c, g);
-        klaunch(k_paint<16>, dim3(grows, n), dim3(256), glds, s, c, g, min_area2);
+        klaunch(k_resolve<16>, dim3(grows, n), dim3(256), glds + 8 * g.WW, s, c, g);   // + the halo row
+        klaunch(k_area<16>, dim3(grows, n), dim3(256), 0, s, c, g);
+        if (back) launch_paint_dilate<16>(c, *back, min_area2, s);
+        else klaunch(k_paint<16>, dim3(grows, n), dim3(256), glds, s, c, g, min_area2);
     }
     return hipGetLastError();
 }
 
 template <int B>
-static hipError_t launch_acc(const BackArgs& a, hipStream_t s)
+static hipError_t launch_acc(const BackArgs& a, hipStream_t s, bool dilated)
 {
-    klaunch(k_dilate<B>, dim3((a.g.WW * a.NBY + 255) / 256, a.n), dim3(256), 0, s, a);
+    if (!dilated) klaunch(k_dilate<B>, dim3((a.g.WW * a.NBY + 255) / 256, a.n), dim3(256), 0, s, a);
     if (a.acc_fast)
         klaunch((k_acc<B, true>), dim3(a.SW, a.NBY), dim3(64), 0, s, a);
     else
@@ -2246,10 +2415,11 @@ static hipError_t launch_acc(const BackArgs& a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_accumulate(const BackArgs& a, hipStream_t s)
+hipError_t launch_accumulate(const BackArgs& a, hipStream_t s, bool dilated)
 {
-    if (a.B == 4) return launch_acc<4>(a, s);
-    if (a.B == 8) return launch_acc<8>(a, s);
+    if (a.B == 4) return launch_acc<4>(a, s, dilated);
+    if (a.B == 8) return launch_acc<8>(a, s, dilated);
+    if (dilated) return hipErrorInvalidValue;   // only the block-major back end has the fused form
     klaunch(k_dilate_rows, dim3((a.g.WW * a.g.H + 255) / 256, a.n), dim3(256), 0, s, a);
     klaunch(k_acc_rows, dim3(a.g.WW, a.g.H), dim3(64), 0, s, a);
     return hipGetLastError();

@@ -59,7 +59,8 @@ class FDWorker(Worker):
 
     def __init__(self, width: int, height: int, *, device: int = 0, stream=None,
                  device_ptrs: bool = False, keep_planes: bool = False, ktiming: bool = False,
-                 max_batch: int = 1, out_format: str = "BGR", fused: bool = True, **kwargs):
+                 max_batch: int = 1, out_format: str = "BGR", fused: bool = True, kept_plane: bool = False,
+                 **kwargs):
         """``width, height``: the scaled frame size (fd:60-61); frames handed to
         :meth:`prime`/:meth:`step` are ``src_width x src_height`` (the video's,
         default the same) and are resized on the GPU (fd:74,91).
@@ -72,10 +73,14 @@ class FDWorker(Worker):
         ``out_format`` "BGR" or "I420": overlay and compressed frames as the
         encoder's 4:2:0 input (DVC_FLAG_OUT_I420). ``fused=False``: outputs in
         one k_out pass instead of the fused front's speculative static-block
-        outputs + k_fix (DVC_FLAG_FD_UNFUSED; same bytes)."""
+        outputs + k_fix (DVC_FLAG_FD_UNFUSED; same bytes). ``kept_plane=True``:
+        the kept mask goes from the contour filter to the dilation through
+        device memory instead of staying on chip (DVC_FLAG_FD_KEPT_PLANE; same
+        bytes)."""
         if out_format not in ("BGR", "I420"):
             raise ValueError(f"out_format {out_format!r}: BGR or I420")
-        flags = (N.DVC_FLAG_OUT_I420 if out_format == "I420" else 0) | (0 if fused else N.DVC_FLAG_FD_UNFUSED)
+        flags = (N.DVC_FLAG_OUT_I420 if out_format == "I420" else 0) | (0 if fused else N.DVC_FLAG_FD_UNFUSED) | \
+            (N.DVC_FLAG_FD_KEPT_PLANE if kept_plane else 0)
         self.out_format = out_format
         W, H = int(width), int(height)
         self.SW = int(kwargs.get("src_width") or width)

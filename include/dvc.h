@@ -95,6 +95,14 @@ extern "C" {
                                      in 4-byte aligned rows; the
                                      environment variable DVC_FD_FUSED=0 sets
                                      this flag for every handle)                */
+#define DVC_FLAG_FD_KEPT_PLANE 0x80u /* FD: carry the kept (filtered) mask from the
+                                     contour filter to the dilation through its
+                                     bit plane in device memory (k_paint, then
+                                     k_dilate) instead of keeping it on chip
+                                     (k_paint_dilate); same bytes. The on-chip
+                                     form applies to block_size 4 and 8 with
+                                     block_size + kernel_size <= 65, without
+                                     DVC_FLAG_KEEP_PLANES                       */
 
 /* ---- frame formats (video I/O) ----------------------------- */
 /* What the worker's frames are. The reference's are packed BGR straight from
@@ -174,9 +182,11 @@ typedef struct dvc_fd_params {
     uint32_t flags;
     uint32_t max_batch; /* 0/1..DVC_MAX_BATCH: frames one device launch covers in
                            dvc_fd_step_batch (longer calls are chunked). Bit
-                           planes are allocated for three batches in flight, the
-                           contour filter's working arrays for one (~20 MB per
-                           1080p frame in all; ~8 GB at 383). */
+                           planes are allocated for four batches in flight, the
+                           contour filter's working arrays for one (per 1080p
+                           frame 4 x 1.05 MB of planes and 17.7 MB of filter
+                           arrays, the filled mask having no plane: ~22 MB in
+                           all; ~8.4 GB at 383). */
     int32_t src_width;  /* 0: = width  */
     int32_t src_height; /* 0: = height */
     int32_t in_format;  /* DVC_FMT_BGR (0) / DVC_FMT_I420 / DVC_FMT_NV12: the frames

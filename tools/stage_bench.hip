@@ -61,7 +61,7 @@ int main(int argc, char** argv)
     void** ptrs[dvc::CclBufs::NARR];
     c.ptrs(ptrs);
     for (int i = 0; i < dvc::CclBufs::NARR; ++i) CK(hipMalloc(ptrs[i], sz[i]));
-    CK(hipMemset(c.gpar, 0, sz[6]));
+    CK(hipMemset(c.gpar, 0, sz[dvc::CclBufs::I_GPAR]));
     c.stats = stats;
     CK(hipMalloc(&c.kocc, (size_t)H * n));   // sparse kept rows, as the handle runs it
     const int B = 4, NBX = (W + B - 1) / B, NBY = (H + B - 1) / B, SW = (NBX + 63) / 64, gs = (W + 3) & ~3;
