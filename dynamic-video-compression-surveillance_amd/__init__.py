@@ -15,4 +15,4 @@ from . import _native  # noqa: F401  (loading is lazy; no CPU fallback)
 from .fd import FDWorker, derive_params  # noqa: F401
 from .of import OFWorker, derive_of_params  # noqa: F401,E402
 from ._native import QualityMeter  # noqa: F401,E402
-from .quality import compare_videos  # noqa: F401,E402
+from .quality import compare_videos, compare_videos_regions  # noqa: F401,E402

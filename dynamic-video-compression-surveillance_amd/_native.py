@@ -118,7 +118,7 @@ def sources() -> list:
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = sources()
-    deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(PKG_DIR, "..", "include", "dvc.h")]
+    deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(PKG_DIR, "..", "include", "*.h"))
     if not force and os.path.exists(LIB_PATH):
         newest = max(os.path.getmtime(d) for d in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
@@ -204,6 +204,10 @@ SIGNATURES = {
     "dvc_copy_rate": (_I, (_I, _Z, _I, _I, _PD)),
 }
 EXPORTS = list(SIGNATURES)
+# What include/dvc_quality_regions.h declares, bound the same way.
+REGION_SIGNATURES = {
+    "dvc_quality_compare_regions": (_I, (_P, _P, _Z, _Z, _P, _Z, _Z, _P, _Z, _Z, _I, _I, _I, _P)),
+}
 # An older build loaded for an A/B run (DVC_LIB_PATH with DVC_ALLOW_ABI_MISMATCH=1)
 # may lack these; FDWorker.ktime_kernel and OFWorker.ktime_kernel fall back.
 OPTIONAL = ("dvc_fd_ktime_kernel", "dvc_fd_graph_stats", "dvc_of_ktime_kernel")
@@ -239,7 +243,7 @@ def lib() -> ctypes.CDLL:
                               "(set DVC_ALLOW_ABI_MISMATCH=1 to load it anyway)")
         import warnings
         warnings.warn(f"{path}: ABI version mismatch accepted (DVC_ALLOW_ABI_MISMATCH=1)")
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **REGION_SIGNATURES}.items():
         if name in OPTIONAL and not hasattr(L, name):
             continue
         fn = getattr(L, name)
@@ -537,6 +541,10 @@ class JpegDecoder(Handle):
 
 # dvc_quality_frame (include/dvc.h) as a numpy record
 QUALITY_FRAME = [("sse", "<u8", (4,)), ("ssim_q32", "<i8"), ("windows", "<u4"), ("pixels", "<u4")]
+# dvc_quality_regions: sse[class][channel] (class 0 kept, 1 static), ssim_q32 / windows of the
+# kept, static and mixed windows, pixels[class]
+QUALITY_REGIONS = [("sse", "<u8", (2, 4)), ("ssim_q32", "<i8", (3,)), ("windows", "<u4", (3,)), ("pixels", "<u4", (2,)),
+                   ("reserved", "<u4")]
 
 
 class QualityMeter(Handle):
@@ -574,6 +582,35 @@ class QualityMeter(Handle):
         out = np.zeros(a.shape[0], QUALITY_FRAME)
         check(lib().dvc_quality_compare(self._h, a.ctypes.data, ap, as_, b.ctypes.data, bp, bs, a.shape[0],
                                         out.ctypes.data))
+        return out
+
+    def compare_regions(self, ref, test, mask, block, partial_static):
+        """:meth:`compare` split by ``mask``, (n, H, W) uint8 (rows >= W bytes apart are
+        read in place): one ``QUALITY_REGIONS`` record per pair, the squared error of
+        the kept and of the static pixels and the SSIM of the kept, static and mixed
+        windows (DESIGN.md "Quality metrics": a block of ``block`` x ``block`` pixels is
+        static iff its mask bytes are all 0; ``partial_static`` 1 applies that to the
+        partial blocks on the right and bottom edges, as the FD worker does, 0 keeps
+        them, as the OF compressor does). Any n: more than ``max_batch`` pairs go in
+        several calls."""
+        import numpy as np
+        a, ap, as_ = self._rows(ref)
+        b, bp, bs = self._rows(test)
+        m = np.asarray(mask)
+        n = a.shape[0]
+        if m.dtype != np.uint8 or m.shape != (n, self.H, self.W) or b.shape[0] != n:
+            raise ValueError(f"{n} reference frames, {b.shape[0]} test frames and masks {m.shape} {m.dtype}: "
+                             f"(n, {self.H}, {self.W}) uint8 masks are needed")
+        ms, mp = m.strides[0], m.strides[1]
+        if m.strides[2] != 1 or mp < self.W or (n > 1 and ms < mp * (self.H - 1) + self.W):
+            m = np.ascontiguousarray(m)
+            ms, mp = m.strides[0], m.strides[1]
+        out = np.zeros(n, QUALITY_REGIONS)
+        for t in range(0, n, self.max_batch):
+            k = min(self.max_batch, n - t)
+            check(lib().dvc_quality_compare_regions(self._h, a[t:].ctypes.data, ap, as_, b[t:].ctypes.data, bp, bs,
+                                                    m[t:].ctypes.data, mp, ms, int(block), int(partial_static), k,
+                                                    out[t:].ctypes.data))
         return out
 
 

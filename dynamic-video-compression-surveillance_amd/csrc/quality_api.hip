@@ -3,6 +3,7 @@
 // compressed output against its source. The arithmetic is DESIGN.md "Quality
 // metrics" (quality_core.h); the kernels are in quality_kernels.hip.
 #include "../../include/dvc.h"
+#include "../../include/dvc_quality_regions.h"
 #include "host_common.h"
 #include "quality_kernels.h"
 
@@ -10,6 +11,8 @@ using dvc_host::fail;
 
 static_assert(sizeof(dvc_quality_frame) == sizeof(dvc::QualityFrame) && sizeof(dvc_quality_frame) == 48,
               "quality_kernels.h restates dvc_quality_frame");
+static_assert(sizeof(dvc_quality_regions) == sizeof(dvc::QualityRegions) && sizeof(dvc_quality_regions) == 112,
+              "quality_kernels.h restates dvc_quality_regions");
 
 struct dvc_quality {
     dvc::QualityGeom g{};
@@ -22,6 +25,28 @@ struct dvc_quality {
     uint8_t *d_a = nullptr, *d_b = nullptr;
     dvc::QualityFrame* d_res = nullptr;
     size_t ip = 0;
+    // dvc_quality_compare_regions, allocated by its first call: the class bits (sized for
+    // block 1, the most rows), sixteen words per tile and frame, and in host-pointer
+    // mode the staged masks (rows of mp bytes) and the records
+    uint32_t* d_cls = nullptr;
+    uint64_t* d_part_r = nullptr;
+    uint8_t* d_m = nullptr;
+    dvc::QualityRegions* d_res_r = nullptr;
+    size_t mp = 0;
+
+    hipError_t regions_memory()
+    {
+        if (d_cls) return hipSuccess;
+        const size_t mb = max_batch, tiles = (size_t)g.tiles_x * g.tiles_y;
+        mp = ((size_t)g.W + 3) & ~(size_t)3;
+        hipError_t e = mem.alloc(&d_part_r, mb * tiles * dvc::kQualityRegionParts * sizeof(uint64_t));
+        if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
+            e = mem.alloc(&d_m, mb * mp * g.H);
+            if (e == hipSuccess) e = mem.alloc(&d_res_r, mb * sizeof(dvc::QualityRegions));
+        }
+        if (e == hipSuccess) e = mem.alloc(&d_cls, mb * dvc::quality_class_words(g.W, g.H, 1) * sizeof(uint32_t));
+        return e;
+    }
 };
 
 extern "C" {
@@ -82,6 +107,43 @@ int dvc_quality_compare(dvc_quality* h, const uint8_t* ref, size_t ref_pitch, si
     HIP_OK(dvc::quality_launch(h->d_a, h->ip, h->ip * H, h->d_b, h->ip, h->ip * H, n, h->g, h->d_part, h->d_res,
                                h->stream.s));
     HIP_OK(hipMemcpyAsync(res, h->d_res, n * sizeof(dvc::QualityFrame), hipMemcpyDeviceToHost, h->stream.s));
+    HIP_OK(hipStreamSynchronize(h->stream.s));
+    return DVC_OK;
+}
+
+int dvc_quality_compare_regions(dvc_quality* h, const uint8_t* ref, size_t ref_pitch, size_t ref_stride,
+                                const uint8_t* test, size_t test_pitch, size_t test_stride, const uint8_t* mask,
+                                size_t mask_pitch, size_t mask_stride, int block, int partial_static, int n,
+                                dvc_quality_regions* results)
+{
+    if (!h || !ref || !test || !mask || !results) return fail(DVC_E_INVALID, "NULL argument");
+    if (n < 1 || n > h->max_batch) return fail(DVC_E_INVALID, "frame count %d outside 1..%d", n, h->max_batch);
+    if (block < 1 || block > dvc::kQualityMaxBlock)
+        return fail(DVC_E_INVALID, "block %d outside 1..%d", block, dvc::kQualityMaxBlock);
+    if (partial_static != 0 && partial_static != 1)
+        return fail(DVC_E_INVALID, "partial_static %d is neither 0 nor 1", partial_static);
+    const size_t W = h->g.W, roww = 3 * W, H = h->g.H;
+    if (ref_pitch < roww || test_pitch < roww || mask_pitch < W) return fail(DVC_E_INVALID, "pitch invalid");
+    if (n > 1 && (ref_stride < ref_pitch * (H - 1) + roww || test_stride < test_pitch * (H - 1) + roww ||
+                  mask_stride < mask_pitch * (H - 1) + W))
+        return fail(DVC_E_INVALID, "frame stride invalid");
+    const bool dev = h->flags & DVC_FLAG_DEVICE_PTRS;
+    if (dev && ((uintptr_t)results & 7)) return fail(DVC_E_INVALID, "results must be 8-byte aligned");
+    HIP_OK(hipSetDevice(h->device));
+    HIP_OK(h->regions_memory());
+    auto* res = reinterpret_cast<dvc::QualityRegions*>(results);
+    if (dev) {
+        HIP_OK(dvc::quality_launch_regions(ref, ref_pitch, ref_stride, test, test_pitch, test_stride, mask, mask_pitch,
+                                           mask_stride, block, partial_static, n, h->g, h->d_cls, h->d_part_r, res,
+                                           h->stream.s));
+        return DVC_OK;
+    }
+    HIP_OK(dvc_host::stage_rows_h2d(h->d_a, h->ip, ref, ref_pitch, ref_stride, roww, H, n, h->stream.s));
+    HIP_OK(dvc_host::stage_rows_h2d(h->d_b, h->ip, test, test_pitch, test_stride, roww, H, n, h->stream.s));
+    HIP_OK(dvc_host::stage_rows_h2d(h->d_m, h->mp, mask, mask_pitch, mask_stride, W, H, n, h->stream.s));
+    HIP_OK(dvc::quality_launch_regions(h->d_a, h->ip, h->ip * H, h->d_b, h->ip, h->ip * H, h->d_m, h->mp, h->mp * H,
+                                       block, partial_static, n, h->g, h->d_cls, h->d_part_r, h->d_res_r, h->stream.s));
+    HIP_OK(hipMemcpyAsync(res, h->d_res_r, n * sizeof(dvc::QualityRegions), hipMemcpyDeviceToHost, h->stream.s));
     HIP_OK(hipStreamSynchronize(h->stream.s));
     return DVC_OK;
 }

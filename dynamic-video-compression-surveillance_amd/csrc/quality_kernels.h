@@ -51,4 +51,32 @@ hipError_t quality_launch(const uint8_t* a, size_t a_pitch, size_t a_stride, con
                           size_t b_stride, int n, const QualityGeom& g, uint64_t* partials, QualityFrame* results,
                           hipStream_t st);
 
+// ---- kept and static regions ----------------------------------------------------
+// What dvc_quality_regions is (include/dvc.h).
+struct QualityRegions {
+    uint64_t sse[2][4];
+    int64_t ssim_q32[3];
+    uint32_t windows[3];
+    uint32_t pixels[2];
+    uint32_t reserved;
+};
+
+// The class bits of a frame: one bit per pixel column and block row (every pixel
+// row of a block row has the same bits), ceil(H / block) rows of ceil(W / 32)
+// words; bit x % 32 of word x / 32 is set where the column's block is static.
+constexpr int kQualityRegionParts = 16;   // words per tile and frame (k_quality_tile_regions)
+constexpr int kQualityMaxBlock = 128;
+inline size_t quality_class_words(int W, int H, int block)
+{
+    return (size_t)((H + block - 1) / block) * (size_t)((W + 31) / 32);
+}
+
+// quality_launch with a mask frame per pair (frame t at mask + t * m_stride, rows
+// of m_pitch >= W bytes) -> results[0..n). cls: n * quality_class_words words,
+// partials: n * tiles_x * tiles_y * kQualityRegionParts words of workspace.
+hipError_t quality_launch_regions(const uint8_t* a, size_t a_pitch, size_t a_stride, const uint8_t* b, size_t b_pitch,
+                                  size_t b_stride, const uint8_t* mask, size_t m_pitch, size_t m_stride, int block,
+                                  int partial_static, int n, const QualityGeom& g, uint32_t* cls, uint64_t* partials,
+                                  QualityRegions* results, hipStream_t st);
+
 }  // namespace dvc

@@ -616,6 +616,8 @@ int dvc_quality_create(int width, int height, int max_batch, int device, void* h
  * when one was joined); dvc_quality_sync waits. */
 int dvc_quality_compare(dvc_quality* h, const uint8_t* ref, size_t ref_pitch, size_t ref_stride, const uint8_t* test,
                         size_t test_pitch, size_t test_stride, int n, dvc_quality_frame* results);
+/* The same figures split into the blocks the workers kept and the blocks they
+ * flattened, on the same handle: include/dvc_quality_regions.h. */
 int dvc_quality_sync(dvc_quality* h);
 void dvc_quality_destroy(dvc_quality* h);
 
