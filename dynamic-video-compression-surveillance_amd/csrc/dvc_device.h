@@ -1,4 +1,5 @@
-// dvc_device.h — device helpers shared by the FD and OF kernels (gfx950).
+// dvc_device.h — device helpers shared by the FD and OF kernels (gfx950);
+// their pixel arithmetic is in px_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,40 +24,6 @@ __device__ __forceinline__ int reflect101(int x, int n)
     if (n == 1) return 0;
     while (x < 0 || x >= n) x = x < 0 ? -x : 2 * n - 2 - x;
     return x;
-}
-
-// OpenCV BGR2GRAY 8U: (1868 B + 9617 G + 4899 R + 2^13) >> 14
-__device__ __forceinline__ uint32_t gray_px(uint32_t b, uint32_t g, uint32_t r)
-{
-    return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
-}
-
-// 4 packed BGR pixels (12 bytes = 3 dwords, little endian) -> 4 packed gray bytes
-__device__ __forceinline__ uint32_t gray4(uint32_t d0, uint32_t d1, uint32_t d2)
-{
-    uint32_t y0 = gray_px(d0 & 255, (d0 >> 8) & 255, (d0 >> 16) & 255);
-    uint32_t y1 = gray_px(d0 >> 24, d1 & 255, (d1 >> 8) & 255);
-    uint32_t y2 = gray_px((d1 >> 16) & 255, d1 >> 24, d2 & 255);
-    uint32_t y3 = gray_px((d2 >> 8) & 255, (d2 >> 16) & 255, d2 >> 24);
-    return y0 | (y1 << 8) | (y2 << 16) | (y3 << 24);
-}
-
-// The same 4 gray bytes with the v_dot4_u32_u8 unit: each coefficient split as
-// 256*hi + lo, so Y*2^14 + 2^13 = (dot4(px, hi) << 8) + dot4(px, lo) + 2^13 per
-// pixel (byte 3 of each operand is multiplied by 0); v_alignbyte puts pixel i's
-// (b, g, r) at bytes 0..2, v_perm packs the four results. Bit-identical to gray4.
-__device__ __forceinline__ uint32_t gray4_dot(uint32_t d0, uint32_t d1, uint32_t d2)
-{
-    constexpr uint32_t LO = 76u | (145u << 8) | (35u << 16);   // 1868, 9617, 4899 mod 256
-    constexpr uint32_t HI = 7u | (37u << 8) | (19u << 16);     // ... div 256
-    const uint32_t p1 = __builtin_amdgcn_alignbyte(d1, d0, 3), p2 = __builtin_amdgcn_alignbyte(d2, d1, 2);
-    const uint32_t p3 = d2 >> 8;
-    auto y = [](uint32_t p) {
-        return ((__builtin_amdgcn_udot4(p, HI, 0u, false) << 8) + __builtin_amdgcn_udot4(p, LO, 8192u, false)) >> 14;
-    };
-    const uint32_t lo = __builtin_amdgcn_perm(y(p1), y(d0), 0x0c0c0400u);
-    const uint32_t hi = __builtin_amdgcn_perm(y(p3), y(p2), 0x0c0c0400u);
-    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
 }
 
 // Order LDS accesses of the lanes of ONE wave (no workgroup barrier): for
@@ -394,31 +361,5 @@ __device__ __forceinline__ void block_dct_quant_pk(float (&X)[B * B], const DctM
             X[i * B + n + 1] = t.y;
         }
 }
-
-// Y (BGR2YCrCb / BGR2GRAY luma) of 4 packed BGR px as four u32, via v_dot4
-// (see gray4_dot).
-__device__ __forceinline__ void luma4(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t (&y)[4])
-{
-    constexpr uint32_t LO = 76u | (145u << 8) | (35u << 16);
-    constexpr uint32_t HI = 7u | (37u << 8) | (19u << 16);
-    const uint32_t p[4] = {d0, __builtin_amdgcn_alignbyte(d1, d0, 3), __builtin_amdgcn_alignbyte(d2, d1, 2), d2 >> 8};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        y[j] = ((__builtin_amdgcn_udot4(p[j], HI, 0u, false) << 8) + __builtin_amdgcn_udot4(p[j], LO, 8192u, false)) >> 14;
-}
-
-// 4 bytes v0..v3 (low byte of each u32) -> the 3 dwords of (v0 v0 v0)(v1 v1 v1)
-// (v2 v2 v2)(v3 v3 v3) packed BGR, i.e. 4 gray pixels as BGR.
-__device__ __forceinline__ void gray_bgr4(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t* out)
-{
-    const uint32_t V = __builtin_amdgcn_perm(__builtin_amdgcn_perm(v3, v2, 0x0c0c0400u),
-                                             __builtin_amdgcn_perm(v1, v0, 0x0c0c0400u), 0x05040100u);
-    out[0] = __builtin_amdgcn_perm(V, V, 0x01000000u);
-    out[1] = __builtin_amdgcn_perm(V, V, 0x02020101u);
-    out[2] = __builtin_amdgcn_perm(V, V, 0x03030302u);
-}
-
-__device__ __forceinline__ int descale14(int v) { return (v + 8192) >> 14; }
-__device__ __forceinline__ uint32_t satu8(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
 }  // namespace dvc

@@ -39,7 +39,7 @@
 #include "fd_kernels.h"
 #include "klaunch.h"
 #include "dct_const.h"
-#include "yuv_px.h"
+#include "px_device.h"
 #include "../../include/dvc.h"
 #include "tune.h"
 
@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(256) k_gray(const uint8_t* __restrict__ bgr, i
     int y = blockIdx.y;
     if (4 * q >= W) return;
     const uint32_t* p = reinterpret_cast<const uint32_t*>(bgr + (size_t)y * pitch + 12 * q);
-    *reinterpret_cast<uint32_t*>(gray + (size_t)y * gs + 4 * q) = gray4(p[0], p[1], p[2]);
+    *reinterpret_cast<uint32_t*>(gray + (size_t)y * gs + 4 * q) = gray4_dot(p[0], p[1], p[2]);
 }
 
 __global__ void __launch_bounds__(256) k_hblur_q8(const uint8_t* __restrict__ src, uint32_t* __restrict__ tmp,
@@ -97,7 +97,6 @@ __global__ void __launch_bounds__(256) k_vblur_q8(const uint32_t* __restrict__ t
 // workgroups in flight for one extra frame read per chunk.
 constexpr int FT_W = 256, FT_Q = FT_W / 4 + 2;
 
-
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
 __device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
@@ -109,29 +108,6 @@ __device__ __forceinline__ uint32_t as_u32(u16x2 v) { return __builtin_bit_cast(
 //   5-tap v   packed u16 lanes (sums <= 16 * 4080 < 2^16), (s + 128) >> 8
 //   threshold |cur - prev| > t per u16 lane as bit 15 of d + (0x7fff - t)
 // The previous blurred gray (fd:133) stays in registers as two u16 pairs.
-// A 4-px quad (x even) of a 4:2:0 surface as loaded (y4 = its luma dword;
-// I420: c1 / c2 = the u16 of U / V samples; NV12: c1 = the dword U0 V0 U1 V1)
-// -> 12 packed BGR bytes (cvtColor YUV2BGR, yuv_px.h)
-template <int FMT>
-__device__ __forceinline__ void quad_bgr(uint32_t y4, uint32_t c1, uint32_t c2, uint32_t o[3])
-{
-    if constexpr (FMT == DVC_FMT_NV12) yuvpx::yuv4_bgr(y4, c1 & 255, (c1 >> 8) & 255, (c1 >> 16) & 255, c1 >> 24, o);
-    else yuvpx::yuv4_bgr(y4, c1 & 255, c2 & 255, (c1 >> 8) & 255, (c2 >> 8) & 255, o);
-}
-
-// gray of a loaded quad: 12 BGR bytes (v0..v2), or a 4:2:0 quad via quad_bgr
-template <int FMT>
-__device__ __forceinline__ uint32_t quad_gray(uint32_t v0, uint32_t v1, uint32_t v2)
-{
-    if constexpr (FMT == DVC_FMT_BGR) {
-        return gray4_dot(v0, v1, v2);
-    } else {
-        uint32_t o[3];
-        quad_bgr<FMT>(v0, v1, v2, o);
-        return gray4_dot(o[0], o[1], o[2]);
-    }
-}
-
 // OUT (fused speculative outputs, FrontOut in fd_kernels.h; NW = 4 or 8): the
 // rows are dealt by block row instead — wave w loads and owns tile rows
 // 4w..4w+3, so each lane holds one 4x4 block of the frame, plus one halo row
@@ -238,84 +214,6 @@ __device__ __forceinline__ void dct8_quad(float* S, int r, const float (&x)[2][8
     wave_sync_lds();   // the scratch is rewritten by the next frame
 }
 
-// One row of a BxB block of an output frame as the encoder's 4:2:0 input
-// (cvtColor BGR2YUV_I420, include/dvc.h DVC_FLAG_OUT_I420): B luma bytes, and
-// on even rows the B/2 chroma samples of the 2x2 quads (their top-left pixel).
-// I420 frame at f: Y plane W x H, then U and V planes of W/2 x H/2.
-template <int B>
-__device__ __forceinline__ void store_i420_row(uint8_t* f, int W, int H, int y, int x, const uint32_t* w)
-{
-    using namespace yuvpx;
-    uint32_t yv[B], uv[B / 2], vv[B / 2];
-#pragma unroll
-    for (int j = 0; j < B; ++j) {
-        const int b = (int)((w[(3 * j) >> 2] >> (8 * ((3 * j) & 3))) & 255);
-        const int g = (int)((w[(3 * j + 1) >> 2] >> (8 * ((3 * j + 1) & 3))) & 255);
-        const int r = (int)((w[(3 * j + 2) >> 2] >> (8 * ((3 * j + 2) & 3))) & 255);
-        yv[j] = luma(b, g, r);
-        if (!(j & 1)) {
-            uv[j >> 1] = chroma_u(b, g, r);
-            vv[j >> 1] = chroma_v(b, g, r);
-        }
-    }
-    uint32_t* yo = reinterpret_cast<uint32_t*>(f + (size_t)y * W + x);
-#pragma unroll
-    for (int d = 0; d < B / 4; ++d)
-        __builtin_nontemporal_store(pack4(yv[4 * d], yv[4 * d + 1], yv[4 * d + 2], yv[4 * d + 3]), yo + d);
-    if (!(y & 1)) {
-        const size_t c = (size_t)W * H + (size_t)(y >> 1) * (W >> 1) + (x >> 1), q = (size_t)(W >> 1) * (H >> 1);
-        if constexpr (B == 4) {
-            __builtin_nontemporal_store((uint16_t)(uv[0] | (uv[1] << 8)), reinterpret_cast<uint16_t*>(f + c));
-            __builtin_nontemporal_store((uint16_t)(vv[0] | (vv[1] << 8)), reinterpret_cast<uint16_t*>(f + c + q));
-        } else {
-#pragma unroll
-            for (int d = 0; d < B / 8; ++d) {
-                __builtin_nontemporal_store(pack4(uv[4 * d], uv[4 * d + 1], uv[4 * d + 2], uv[4 * d + 3]),
-                                            reinterpret_cast<uint32_t*>(f + c) + d);
-                __builtin_nontemporal_store(pack4(vv[4 * d], vv[4 * d + 1], vv[4 * d + 2], vv[4 * d + 3]),
-                                            reinterpret_cast<uint32_t*>(f + c + q) + d);
-            }
-        }
-    }
-}
-
-
-// BGR2YUV_I420 luma of the 4 packed BGR pixels of a quad row (dwords d0..d2),
-// as v_dot4 with the 20-bit coefficients split into bytes: the same integer as
-// yuvpx::luma (no saturation needed: 16 <= Y <= 235 for every BGR).
-__device__ __forceinline__ uint32_t luma4_i420(uint32_t d0, uint32_t d1, uint32_t d2)
-{
-    using namespace yuvpx;
-    constexpr uint32_t K0 = (CBY & 255) | ((CGY & 255) << 8) | ((CRY & 255) << 16);
-    constexpr uint32_t K1 = ((CBY >> 8) & 255) | (((CGY >> 8) & 255) << 8) | (((CRY >> 8) & 255) << 16);
-    constexpr uint32_t K2 = (CBY >> 16) | ((CGY >> 16) << 8) | ((CRY >> 16) << 16);
-    static_assert((CBY >> 24) == 0 && (CGY >> 24) == 0 && (CRY >> 24) == 0 && CBY > 0 && CGY > 0 && CRY > 0,
-                  "luma coefficients: three bytes each");
-    static_assert((255 * (CBY + CGY + CRY) + HALF + (16 << SHIFT)) >> SHIFT <= 255, "luma never saturates");
-    const uint32_t p[4] = {d0, __builtin_amdgcn_alignbyte(d1, d0, 3), __builtin_amdgcn_alignbyte(d2, d1, 2), d2 >> 8};
-    uint32_t y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t t2 = __builtin_amdgcn_udot4(p[j] & 0x00ffffffu, K2, 0u, false);
-        const uint32_t t1 = __builtin_amdgcn_udot4(p[j] & 0x00ffffffu, K1, t2 << 8, false);
-        y[j] = __builtin_amdgcn_udot4(p[j] & 0x00ffffffu, K0, (t1 << 8) + (uint32_t)(HALF + (16 << SHIFT)), false) >> SHIFT;
-    }
-    return yuvpx::pack4(y[0], y[1], y[2], y[3]);
-}
-// chroma of pixels 0 and 2 of the quad row (the top-left pixels of its two
-// 2x2 quads): U0 | U2 << 8 in the low half, V0 | V2 << 8 in the high half
-__device__ __forceinline__ uint32_t chroma2_i420(uint32_t d0, uint32_t d1, uint32_t d2)
-{
-    using namespace yuvpx;
-    const int b0 = d0 & 255, g0 = (d0 >> 8) & 255, r0 = (d0 >> 16) & 255;
-    const int b2 = (d1 >> 16) & 255, g2 = d1 >> 24, r2 = d2 & 255;   // bytes 6, 7, 8
-    return chroma_u(b0, g0, r0) | (chroma_u(b2, g2, r2) << 8) | (chroma_v(b0, g0, r0) << 16) |
-           (chroma_v(b2, g2, r2) << 24);
-}
-// a gray pixel (R = G = B = u) has U = V = 128: both chroma rows of coefficients sum to 1
-static_assert(yuvpx::CRU + yuvpx::CGU + yuvpx::CBU == 1 && yuvpx::CBU + yuvpx::CGV + yuvpx::CBV == 1,
-              "gray chroma is 128");
-
 #ifndef DVC_FRONT_WGS_YUV_OI   // 4:2:0 input, I420 outputs
 #define DVC_FRONT_WGS_YUV_OI 4
 #endif
@@ -395,6 +293,7 @@ __global__ void __launch_bounds__(64 * NW, OUT ? (OB == 8 ? DVC_FRONT_WGS_B8 : P
     auto row_off = [&](int y, int xq, uint32_t& o, uint32_t& co) {
         if constexpr (YUV) {
             o = (uint32_t)(y * pitch + xq);
+            // chroma_off<FMT>(sf, y, xq) restated: the call's sum stays 64-bit, k_front's stream is kept as it is
             co = (uint32_t)(sf.uoff + (size_t)(y >> 1) * sf.cpitch + (FMT == DVC_FMT_NV12 ? xq : xq >> 1));
         } else {
             o = (uint32_t)(y * pitch + 3 * xq);
@@ -413,20 +312,6 @@ __global__ void __launch_bounds__(64 * NW, OUT ? (OB == 8 ? DVC_FRONT_WGS_B8 : P
     // one frame's quads in registers; PF sets in flight (PF - 1 frames of
     // prefetch beyond the one being converted)
     struct Quads { uint32_t v0[NR], v1[NR], v2[NR], h0, h1, h2; };
-    auto load_quad = [&](const uint8_t* f, uint32_t o, uint32_t co, uint32_t& a, uint32_t& b, uint32_t& c) {
-        if constexpr (FMT == DVC_FMT_BGR) {
-            const uint3 q = *reinterpret_cast<const uint3*>(f + o);
-            a = q.x; b = q.y; c = q.z;
-        } else if constexpr (FMT == DVC_FMT_NV12) {
-            a = *reinterpret_cast<const uint32_t*>(f + o);
-            b = *reinterpret_cast<const uint32_t*>(f + co);
-            c = 0;
-        } else {
-            a = *reinterpret_cast<const uint32_t*>(f + o);
-            b = *reinterpret_cast<const uint16_t*>(f + co);
-            c = *reinterpret_cast<const uint16_t*>(f + co + dv);
-        }
-    };
     // the offsets pass through voff in place once per frame (no copies): every
     // load and store below is a uniform base + a 32-bit VGPR offset
     auto load = [&](Quads& qs, const uint8_t* f) {
@@ -434,11 +319,11 @@ __global__ void __launch_bounds__(64 * NW, OUT ? (OB == 8 ? DVC_FRONT_WGS_B8 : P
         for (int j = 0; j < NR; ++j) {
             off[j] = voff(off[j]);
             if constexpr (YUV) coff[j] = voff(coff[j]);
-            load_quad(f, off[j], coff[j], qs.v0[j], qs.v1[j], qs.v2[j]);
+            load_quad<FMT>(f + off[j], f + coff[j], dv, qs.v0[j], qs.v1[j], qs.v2[j]);
         }
         hoff = voff(hoff);
         if constexpr (YUV) hcoff = voff(hcoff);
-        load_quad(f, hoff, hcoff, qs.h0, qs.h1, qs.h2);
+        load_quad<FMT>(f + hoff, f + hcoff, dv, qs.h0, qs.h1, qs.h2);
     };
     Quads qa, qb;
     load(qa, bgr + (size_t)t_begin * fstride);
@@ -686,7 +571,7 @@ __global__ void __launch_bounds__(64 * NW, OUT ? (OB == 8 ? DVC_FRONT_WGS_B8 : P
                         uint32_t yv[4];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) yv[j] = yuvpx::luma((int)u[j], (int)u[j], (int)u[j]);
-                        __builtin_nontemporal_store(yuvpx::pack4(yv[0], yv[1], yv[2], yv[3]),
+                        __builtin_nontemporal_store(pack4(yv[0], yv[1], yv[2], yv[3]),
                                                     reinterpret_cast<uint32_t*>(o + oro[i]));
                         if (!(i & 1)) {
                             __builtin_nontemporal_store((uint16_t)0x8080u, reinterpret_cast<uint16_t*>(o + cro[i >> 1]));
@@ -1605,25 +1490,17 @@ __device__ __forceinline__ void out_tile(const BackArgs& a, int t, int tx, int t
         }
     } else {
 #pragma unroll
-        for (int i = 0; i < B; i += 2) {
-            const uint8_t* cr = f + a.sf.uoff + (size_t)((by + i) >> 1) * a.sf.cpitch + (FMT == DVC_FMT_NV12 ? bx : bx / 2);
-            uint32_t c1[B / 4], c2[B / 4];
+        for (int i = 0; i < B; i += 2) {   // a row pair shares its chroma row (the second row's loads of it are merged)
+            const uint8_t* pc = f + chroma_off<FMT>(a.sf, by + i, bx);
 #pragma unroll
-            for (int d = 0; d < B / 4; ++d) {
-                if constexpr (FMT == DVC_FMT_NV12) {
-                    c1[d] = reinterpret_cast<const uint32_t*>(cr)[d];
-                    c2[d] = 0;
-                } else {
-                    c1[d] = reinterpret_cast<const uint16_t*>(cr)[d];
-                    c2[d] = reinterpret_cast<const uint16_t*>(cr + (a.sf.voff - a.sf.uoff))[d];
+            for (int k = 0; k < 2; ++k)
+#pragma unroll
+                for (int d = 0; d < B / 4; ++d) {
+                    uint32_t y4, c1, c2;
+                    load_quad<FMT>(f + (size_t)(by + i + k) * a.pitch + bx + 4 * d, pc + (FMT == DVC_FMT_NV12 ? 4 : 2) * d,
+                                   a.sf.voff - a.sf.uoff, y4, c1, c2);
+                    quad_bgr<FMT>(y4, c1, c2, &px[i + k][3 * d]);
                 }
-            }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const uint32_t* yr = reinterpret_cast<const uint32_t*>(f + (size_t)(by + i + k) * a.pitch + bx);
-#pragma unroll
-                for (int d = 0; d < B / 4; ++d) quad_bgr<FMT>(yr[d], c1[d], c2[d], &px[i + k][3 * d]);
-            }
         }
     }
     // overlay (fd:110-111): (0,0,255) where acc > 127
@@ -1650,15 +1527,10 @@ __device__ __forceinline__ void out_tile(const BackArgs& a, int t, int tx, int t
                 for (int j = 0; j < B; ++j) {
                     const bool r = (red[i] >> j) & 1u;
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const int bi = 3 * j + c;
-                        const uint32_t v = (px[i][bi >> 2] >> (8 * (bi & 3))) & 255;
-                        ob[bi] = r ? (c == 2 ? 255 : 0) : (uint8_t)v;
-                    }
+                    for (int c = 0; c < 3; ++c) ob[3 * j + c] = r ? (c == 2 ? 255 : 0) : (uint8_t)bgr_at(px[i], j, c);
                 }
 #pragma unroll
-                for (int d = 0; d < 3 * B / 4; ++d)
-                    ow[d] = ob[4 * d] | (ob[4 * d + 1] << 8) | (ob[4 * d + 2] << 16) | ((uint32_t)ob[4 * d + 3] << 24);
+                for (int d = 0; d < 3 * B / 4; ++d) ow[d] = pack_bytes(ob[4 * d], ob[4 * d + 1], ob[4 * d + 2], ob[4 * d + 3]);
             }
             if (a.out_i420) store_i420_row<B>(ovf, W, H, by + i, bx, ow);
             else store_row<3 * B / 4>(ovf + (size_t)(by + i) * a.opitch + 3 * bx, ow, a.obytes);
@@ -1676,7 +1548,7 @@ __device__ __forceinline__ void out_tile(const BackArgs& a, int t, int tx, int t
             for (int i = 0; i < B; ++i)
 #pragma unroll
                 for (int qd = 0; qd < B / 4; ++qd) {
-                    // 1868 + 9617 + 4899 = 2^14: Y of u8 input is in 0..255, no saturation
+                    // Y of u8 input is in 0..255, no saturation (color_core.h)
                     uint32_t y[4];
                     luma4(px[i][3 * qd], px[i][3 * qd + 1], px[i][3 * qd + 2], y);
 #pragma unroll
@@ -1696,24 +1568,7 @@ __device__ __forceinline__ void out_tile(const BackArgs& a, int t, int tx, int t
                 }
         } else {
 #pragma unroll
-            for (int i = 0; i < B; ++i) {
-                uint8_t ob[3 * B];
-#pragma unroll
-                for (int j = 0; j < B; ++j) {
-                    const int b = (px[i][(3 * j) >> 2] >> (8 * ((3 * j) & 3))) & 255;
-                    const int gg = (px[i][(3 * j + 1) >> 2] >> (8 * ((3 * j + 1) & 3))) & 255;
-                    const int r = (px[i][(3 * j + 2) >> 2] >> (8 * ((3 * j + 2) & 3))) & 255;
-                    const int yv = descale14(b * 1868 + gg * 9617 + r * 4899);
-                    const int cr = (int)satu8(descale14((r - yv) * 11682 + (128 << 14))) - 128;
-                    const int cb = (int)satu8(descale14((b - yv) * 9241 + (128 << 14))) - 128;
-                    ob[3 * j] = (uint8_t)satu8(yv + descale14(cb * 29049));
-                    ob[3 * j + 1] = (uint8_t)satu8(yv + descale14(cb * -5636 + cr * -11698));
-                    ob[3 * j + 2] = (uint8_t)satu8(yv + descale14(cr * 22987));
-                }
-#pragma unroll
-                for (int d = 0; d < 3 * B / 4; ++d)
-                    cw[i][d] = ob[4 * d] | (ob[4 * d + 1] << 8) | (ob[4 * d + 2] << 16) | ((uint32_t)ob[4 * d + 3] << 24);
-            }
+            for (int i = 0; i < B; ++i) ycrcb_round_trip_row<B>(px[i], cw[i]);
         }
 #pragma unroll
         for (int i = 0; i < B; ++i) {
@@ -1772,6 +1627,7 @@ __device__ __forceinline__ void fix4_load(const BackArgs& a, int t, int row, int
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int y = 4 * rowc + i;
+            // chroma_off<FMT>, load_quad<FMT> restated in 32-bit offsets (their 64-bit sums: +1 SGPR spill, I420)
             const uint32_t y4 = *reinterpret_cast<const uint32_t*>(f + (uint32_t)(y * a.pitch + xq));
             const uint32_t cr = (uint32_t)(a.sf.uoff + (size_t)(y >> 1) * a.sf.cpitch + (FMT == DVC_FMT_NV12 ? xq : xq / 2));
             uint32_t c1, c2 = 0;
@@ -1818,23 +1674,8 @@ __device__ __forceinline__ void fix4_store(const BackArgs& a, int t, int row, in
     if (a.compressed) {   // not static: the YCrCb -> BGR round trip of every pixel
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            uint8_t ob[12];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int bb = (b.px[i][(3 * j) >> 2] >> (8 * ((3 * j) & 3))) & 255;
-                const int gg = (b.px[i][(3 * j + 1) >> 2] >> (8 * ((3 * j + 1) & 3))) & 255;
-                const int rr = (b.px[i][(3 * j + 2) >> 2] >> (8 * ((3 * j + 2) & 3))) & 255;
-                const int yv = descale14(bb * 1868 + gg * 9617 + rr * 4899);
-                const int cr = (int)satu8(descale14((rr - yv) * 11682 + (128 << 14))) - 128;
-                const int cb = (int)satu8(descale14((bb - yv) * 9241 + (128 << 14))) - 128;
-                ob[3 * j] = (uint8_t)satu8(yv + descale14(cb * 29049));
-                ob[3 * j + 1] = (uint8_t)satu8(yv + descale14(cb * -5636 + cr * -11698));
-                ob[3 * j + 2] = (uint8_t)satu8(yv + descale14(cr * 22987));
-            }
             uint32_t cw[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-                cw[d] = ob[4 * d] | (ob[4 * d + 1] << 8) | (ob[4 * d + 2] << 16) | ((uint32_t)ob[4 * d + 3] << 24);
+            ycrcb_round_trip_row<4>(b.px[i], cw);
             if constexpr (OI) store_i420_row<4>(a.compressed + fo, a.g.W, a.g.H, 4 * row + i, 4 * bx, cw);
             else store_row<3>(a.compressed + fo + (o + (uint32_t)(i * a.opitch)), cw, 0);
         }
@@ -2020,8 +1861,6 @@ struct GenRegion {
     int jbx, jby, njx;
 };
 
-__device__ __forceinline__ int luma_px(int b, int g, int r) { return descale14(b * 1868 + g * 9617 + r * 4899); }
-
 __global__ void __launch_bounds__(256) k_out_gen(BackArgs a, GenRegion R, int fast)
 {
     extern __shared__ __attribute__((aligned(16))) float lds_g[];
@@ -2091,8 +1930,8 @@ __global__ void __launch_bounds__(256) k_out_gen(BackArgs a, GenRegion R, int fa
             cg = px[1];
             cr = px[2];
         } else {   // a 4:2:0 surface read in place
-            const size_t c = (size_t)(y >> 1) * a.sf.cpitch + (a.sf.fmt == DVC_FMT_NV12 ? (x & ~1) : (x >> 1));
-            yuvpx::yuv_px_bgr(f[(size_t)y * a.pitch + x], f[a.sf.uoff + c], f[a.sf.voff + c], cb, cg, cr);
+            const size_t c = chroma_off(a.sf, y, x);
+            yuvpx::yuv_px_bgr(f[(size_t)y * a.pitch + x], f[c], f[c + (a.sf.voff - a.sf.uoff)], cb, cg, cr);
         }
         if (a.overlay) {
             bool red;
@@ -2110,16 +1949,10 @@ __global__ void __launch_bounds__(256) k_out_gen(BackArgs a, GenRegion R, int fa
             o[1] = red ? 0 : (uint8_t)cg;
             o[2] = red ? 255 : (uint8_t)cr;
         }
-        const int yv = luma_px(cb, cg, cr);
         if (flag[b] == 1) {
-            X[e] = (float)(yv - 128);
+            X[e] = (float)((int)gray_px(cb, cg, cr) - 128);
         } else if (a.compressed) {
-            const int crv = (int)satu8(descale14((cr - yv) * 11682 + (128 << 14))) - 128;
-            const int cbv = (int)satu8(descale14((cb - yv) * 9241 + (128 << 14))) - 128;
-            uint8_t* o = a.compressed + (size_t)t * a.ostride + (size_t)y * a.opitch + 3 * x;
-            o[0] = (uint8_t)satu8(yv + descale14(cbv * 29049));
-            o[1] = (uint8_t)satu8(yv + descale14(cbv * -5636 + crv * -11698));
-            o[2] = (uint8_t)satu8(yv + descale14(crv * 22987));
+            ycrcb_round_trip(cb, cg, cr, a.compressed + (size_t)t * a.ostride + (size_t)y * a.opitch + 3 * x);
         }
     }
     __syncthreads();

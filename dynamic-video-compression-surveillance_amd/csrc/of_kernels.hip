@@ -39,7 +39,7 @@
 #include "dvc_device.h"
 #include "of_kernels.h"
 #include "dct_const.h"
-#include "yuv_px.h"
+#include "px_device.h"
 #include "tune.h"
 
 namespace dvc {
@@ -196,31 +196,6 @@ __device__ __forceinline__ void poly_tile(const float* sI, float* sv, const Poly
 // (PN+1) halo, the level-0 smoothing (GaussianBlur 3x3, sigma 0 -> taps
 // (0.25, 0.5, 0.25), BORDER_REFLECT_101) over tile + PN halo, then the
 // polynomial expansion. blockIdx.z = frame of the batch.
-// Gray of 4 px at column px of row y of frame f: 12 packed BGR bytes, or a
-// 4:2:0 quad — its luma dword and chroma (I420: a u16 of U and of V; NV12: the
-// UVUV dword) through cvtColor YUV2BGR (yuv_px.h), then BGR2GRAY (of:71).
-template <int FMT>
-__device__ __forceinline__ uint32_t of_quad_gray(const uint8_t* f, int y, int px, int pitch, const SrcFmt& sf)
-{
-    if constexpr (FMT == DVC_FMT_BGR) {
-        const uint3 v = *reinterpret_cast<const uint3*>(f + (size_t)y * pitch + 3 * px);
-        return gray4_dot(v.x, v.y, v.z);
-    } else {
-        const uint32_t y4 = *reinterpret_cast<const uint32_t*>(f + (size_t)y * pitch + px);
-        const uint8_t* c = f + sf.uoff + (size_t)(y >> 1) * sf.cpitch;
-        uint32_t o[3];
-        if constexpr (FMT == DVC_FMT_NV12) {
-            const uint32_t uv = *reinterpret_cast<const uint32_t*>(c + px);
-            yuvpx::yuv4_bgr(y4, uv & 255, (uv >> 8) & 255, (uv >> 16) & 255, uv >> 24, o);
-        } else {
-            const uint32_t u = *reinterpret_cast<const uint16_t*>(c + (px >> 1));
-            const uint32_t v = *reinterpret_cast<const uint16_t*>(c + (sf.voff - sf.uoff) + (px >> 1));
-            yuvpx::yuv4_bgr(y4, u & 255, v & 255, u >> 8, v >> 8, o);
-        }
-        return gray4_dot(o[0], o[1], o[2]);
-    }
-}
-
 // LDS rows of the level-0 tile: the smoothed image and the vertical sums padded
 // to whole 16-B groups of 4 columns (IW = 74 -> 76 at poly_n 5), and the gray
 // kept as bytes, so that the blur and the vertical polynomial part run 4
@@ -254,7 +229,11 @@ __device__ __forceinline__ void front0_tile(const OfGeom& g, const Level& lv, ui
         // (pitch >= 3 * roundup(W, 4)), its gray values land in the gray rows'
         // padding (GP) and in LDS columns the clamped / reflected taps never read
         if (!INT && (y < 0 || y >= H || px < 0 || px >= W)) continue;
-        const uint32_t gq = of_quad_gray<FMT>(f, y, px, pitch, sf);   // of:71 BGR2GRAY of 4 px
+        // of:71 BGR2GRAY of 4 px: 12 packed BGR bytes, or a 4:2:0 quad through cvtColor YUV2BGR
+        uint32_t v0, v1, v2;
+        load_quad<FMT>(f + (size_t)y * pitch + (FMT == DVC_FMT_BGR ? 3 * px : px), f + chroma_off<FMT>(sf, y, px),
+                       sf.voff - sf.uoff, v0, v1, v2);
+        const uint32_t gq = quad_gray<FMT>(v0, v1, v2);
         *reinterpret_cast<uint32_t*>(sgb + i * GW + 4 * q) = gq;
         if (i >= HG && i < HG + PT_H && px >= x0 && px < x0 + PT_W)
             *reinterpret_cast<uint32_t*>(go + (size_t)y * g.GP + px) = gq;
@@ -2195,7 +2174,7 @@ __device__ __forceinline__ void transpose8(float* S, int r, const float (&v)[8],
 }
 
 // OI: the compressed frame as the encoder's I420 input (DVC_FLAG_OUT_I420,
-// cvtColor BGR2YUV_I420 of the BGR frame: yuv_px.h) as a template parameter, so
+// cvtColor BGR2YUV_I420 of the BGR frame: color_core.h) as a template parameter, so
 // the BGR instantiation carries none of it. The lane's 8 luma bytes go out as
 // two dwords; lanes of even rows hold the top-left pixel of each 2x2 quad at
 // j = 0, 2, 4, 6 and store its 4 U and 4 V samples — no cross-lane traffic.
@@ -2243,13 +2222,12 @@ __global__ void __launch_bounds__(256) k_of_out(OfGeom g, OfBufs B, OfOutArgs o)
         if (o.sf.fmt != DVC_FMT_BGR) {
             // a 4:2:0 surface read in place: the 8 px's luma (2 dwords, aligned:
             // pitch % 4 == 0, bx % 8 == 0) and the 4 chroma pairs of their 2x2
-            // quads, cvtColor YUV2BGR (yuv_px.h) into the 24 BGR bytes
+            // quads, cvtColor YUV2BGR (px_device.h) into the 24 BGR bytes
             const uint8_t* f = o.bgr + (size_t)t * o.fstride;
             const uint8_t* yr = f + (size_t)(act ? y : 0) * o.pitch + (act ? bx : 0);
-            const uint8_t* c = f + o.sf.uoff + (size_t)((act ? y : 0) >> 1) * o.sf.cpitch;
             const size_t dv = o.sf.voff - o.sf.uoff;
             const int cst = o.sf.fmt == DVC_FMT_NV12 ? 2 : 1;   // bytes between chroma samples
-            const uint8_t* cu = c + (size_t)(act ? bx : 0) / 2 * cst;
+            const uint8_t* cu = f + chroma_off(o.sf, act ? y : 0, act ? bx : 0);
             uint32_t y8[2] = {0, 0};
             int us[4] = {0, 0, 0, 0}, vs[4] = {0, 0, 0, 0};
             if (np == 8) {
@@ -2274,15 +2252,8 @@ __global__ void __launch_bounds__(256) k_of_out(OfGeom g, OfBufs B, OfOutArgs o)
             for (int k = 0; k < 3 * np; ++k) px[k >> 2] |= (uint32_t)src8[k] << (8 * (k & 3));
         }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int b = (px[(3 * j) >> 2] >> (8 * ((3 * j) & 3))) & 255;
-            const int gg = (px[(3 * j + 1) >> 2] >> (8 * ((3 * j + 1) & 3))) & 255;
-            const int rr = (px[(3 * j + 2) >> 2] >> (8 * ((3 * j + 2) & 3))) & 255;
-            const int yv = descale14(b * 1868 + gg * 9617 + rr * 4899);
-            ch[0][j] = yv;
-            ch[1][j] = (int)satu8(descale14((rr - yv) * 11682 + (128 << 14)));
-            ch[2][j] = (int)satu8(descale14((b - yv) * 9241 + (128 << 14)));
-        }
+        for (int j = 0; j < 8; ++j)
+            bgr_to_ycrcb((int)bgr_at(px, j, 0), (int)bgr_at(px, j, 1), (int)bgr_at(px, j, 2), ch[0][j], ch[1][j], ch[2][j]);
     }
     const bool sfull = any == 0 && bx + 8 <= W && by + 8 <= H;   // uniform per group
     if (sfull) {   // of:158-168, Y, Cr and Cb
@@ -2326,15 +2297,14 @@ __global__ void __launch_bounds__(256) k_of_out(OfGeom g, OfBufs B, OfOutArgs o)
         uint32_t yo[8], uo[4], vo[4];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {   // as below, then BGR2YUV_I420 of the pixel
-            const int yv = ch[0][j], cr = ch[1][j] - 128, cb = ch[2][j] - 128;
-            uint32_t b = satu8(yv + descale14(cb * 29049));
-            uint32_t gg = satu8(yv + descale14(cb * -5636 + cr * -11698));
-            uint32_t rr = satu8(yv + descale14(cr * 22987));
-            if (sfull) b = gg = rr = gray_px(b, gg, rr);
-            yo[j] = yuvpx::luma((int)b, (int)gg, (int)rr);
+            uint8_t p[3];
+            ycrcb_to_bgr(ch[0][j], ch[1][j], ch[2][j], p);
+            int b = p[0], gg = p[1], rr = p[2];
+            if (sfull) b = gg = rr = (int)gray_px(b, gg, rr);
+            yo[j] = yuvpx::luma(b, gg, rr);
             if (!(j & 1)) {
-                uo[j >> 1] = yuvpx::chroma_u((int)b, (int)gg, (int)rr);
-                vo[j >> 1] = yuvpx::chroma_v((int)b, (int)gg, (int)rr);
+                uo[j >> 1] = yuvpx::chroma_u(b, gg, rr);
+                vo[j >> 1] = yuvpx::chroma_v(b, gg, rr);
             }
         }
         // frame t: Y plane W x H, then U and V planes of W/2 x H/2 (W, H even: np is even)
@@ -2342,8 +2312,8 @@ __global__ void __launch_bounds__(256) k_of_out(OfGeom g, OfBufs B, OfOutArgs o)
         uint8_t* yp = f + (size_t)y * W + bx;
         if (np == 8 && ((uintptr_t)yp & 3) == 0) {
             uint32_t* d = reinterpret_cast<uint32_t*>(yp);
-            d[0] = yuvpx::pack4(yo[0], yo[1], yo[2], yo[3]);
-            d[1] = yuvpx::pack4(yo[4], yo[5], yo[6], yo[7]);
+            d[0] = pack4(yo[0], yo[1], yo[2], yo[3]);
+            d[1] = pack4(yo[4], yo[5], yo[6], yo[7]);
         } else {   // rows of W bytes: W % 4 != 0 leaves odd rows unaligned
 #pragma unroll
             for (int j = 0; j < 8; ++j)
@@ -2353,8 +2323,8 @@ __global__ void __launch_bounds__(256) k_of_out(OfGeom g, OfBufs B, OfOutArgs o)
         uint8_t* up = f + (size_t)W * H + (size_t)(y >> 1) * (W >> 1) + (bx >> 1);
         uint8_t* vp = up + (size_t)(W >> 1) * (H >> 1);
         if (np == 8 && (((uintptr_t)up | (uintptr_t)vp) & 3) == 0) {
-            *reinterpret_cast<uint32_t*>(up) = yuvpx::pack4(uo[0], uo[1], uo[2], uo[3]);
-            *reinterpret_cast<uint32_t*>(vp) = yuvpx::pack4(vo[0], vo[1], vo[2], vo[3]);
+            *reinterpret_cast<uint32_t*>(up) = pack4(uo[0], uo[1], uo[2], uo[3]);
+            *reinterpret_cast<uint32_t*>(vp) = pack4(vo[0], vo[1], vo[2], vo[3]);
         } else {   // chroma rows of W/2 bytes: W % 8 != 0
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -2368,10 +2338,9 @@ __global__ void __launch_bounds__(256) k_of_out(OfGeom g, OfBufs B, OfOutArgs o)
     uint8_t ob[24];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {   // YCrCb -> BGR (of:170-171); static blocks -> gray -> BGR (of:174-183)
-        const int yv = ch[0][j], cr = ch[1][j] - 128, cb = ch[2][j] - 128;
-        uint32_t b = satu8(yv + descale14(cb * 29049));
-        uint32_t gg = satu8(yv + descale14(cb * -5636 + cr * -11698));
-        uint32_t rr = satu8(yv + descale14(cr * 22987));
+        uint8_t p[3];
+        ycrcb_to_bgr(ch[0][j], ch[1][j], ch[2][j], p);
+        uint32_t b = p[0], gg = p[1], rr = p[2];
         if (sfull) b = gg = rr = gray_px(b, gg, rr);
         ob[3 * j] = (uint8_t)b;
         ob[3 * j + 1] = (uint8_t)gg;
@@ -2382,7 +2351,7 @@ __global__ void __launch_bounds__(256) k_of_out(OfGeom g, OfBufs B, OfOutArgs o)
         uint32_t* d = reinterpret_cast<uint32_t*>(d8);
 #pragma unroll
         for (int q = 0; q < 6; ++q)
-            d[q] = ob[4 * q] | (ob[4 * q + 1] << 8) | (ob[4 * q + 2] << 16) | ((uint32_t)ob[4 * q + 3] << 24);
+            d[q] = pack_bytes(ob[4 * q], ob[4 * q + 1], ob[4 * q + 2], ob[4 * q + 3]);
     } else {   // rows of 3W bytes: W % 4 != 0 leaves odd rows unaligned
         for (int k = 0; k < 3 * np; ++k) d8[k] = ob[k];
     }
@@ -2539,6 +2508,27 @@ hipError_t of_launch_pyramid(const OfGeom& g, const Level* lv, const OfBufs& b, 
 // the gather form spent four 8-B vector-memory loads per pixel, texture-
 // addresser bound (~4x the time of its 8-B/px stores). Same products, same
 // order, so the same bits.
+// Shared by both kernels below: one output pixel from its four coarse neighbours (a0, a1 of the upper
+// source row, b0, b1 of the lower) and its taps into v[0..1]; a lane's four pixels (x0 % 4 == 0) out to o.
+__device__ __forceinline__ void flow_up_px(float2 a0, float2 a1, float2 b0, float2 b1, const LinTap& tx,
+                                           const LinTap& ty, float up, float* v)
+{
+    const float t0x = a0.x * tx.w0 + a1.x * tx.w1, t1x = b0.x * tx.w0 + b1.x * tx.w1;
+    const float t0y = a0.y * tx.w0 + a1.y * tx.w1, t1y = b0.y * tx.w0 + b1.y * tx.w1;
+    v[0] = (t0x * ty.w0 + t1x * ty.w1) * up;
+    v[1] = (t0y * ty.w0 + t1y * ty.w1) * up;
+}
+__device__ __forceinline__ void flow_up_store(float* o, const float (&v)[8], int x0, int w)
+{
+    if (x0 + 4 <= w && !(w & 1)) {   // 16-B aligned: x0 % 4 == 0 and rows of an even width
+        *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    } else {   // the row's last lane, or rows of an odd width (8-B aligned only)
+        const int np = min(4, w - x0);
+        for (int k = 0; k < np; ++k) *reinterpret_cast<float2*>(o + 2 * k) = make_float2(v[2 * k], v[2 * k + 1]);
+    }
+}
+
 __global__ void __launch_bounds__(256) k_flow_up_lds(FlowArgs A, float* __restrict__ out)
 {
     extern __shared__ __attribute__((aligned(16))) float2 sup[];
@@ -2569,21 +2559,9 @@ __global__ void __launch_bounds__(256) k_flow_up_lds(FlowArgs A, float* __restri
             const float2* rb = sup + (ty.s1 - r0) * sw;
             float v[8];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float2 a0 = ra[tx[k].s0], a1 = ra[tx[k].s1], b0 = rb[tx[k].s0], b1 = rb[tx[k].s1];
-                const float t0x = a0.x * tx[k].w0 + a1.x * tx[k].w1, t1x = b0.x * tx[k].w0 + b1.x * tx[k].w1;
-                const float t0y = a0.y * tx[k].w0 + a1.y * tx[k].w1, t1y = b0.y * tx[k].w0 + b1.y * tx[k].w1;
-                v[2 * k] = (t0x * ty.w0 + t1x * ty.w1) * A.g.up;
-                v[2 * k + 1] = (t0y * ty.w0 + t1y * ty.w1) * A.g.up;
-            }
-            float* o = out + ((size_t)t * w * h + (size_t)y * w + x0) * 2;
-            if (x0 + 4 <= w && !(w & 1)) {
-                *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-                *reinterpret_cast<float4*>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
-            } else {
-                const int np = min(4, w - x0);
-                for (int k = 0; k < np; ++k) *reinterpret_cast<float2*>(o + 2 * k) = make_float2(v[2 * k], v[2 * k + 1]);
-            }
+            for (int k = 0; k < 4; ++k)
+                flow_up_px(ra[tx[k].s0], ra[tx[k].s1], rb[tx[k].s0], rb[tx[k].s1], tx[k], ty, A.g.up, v + 2 * k);
+            flow_up_store(out + ((size_t)t * w * h + (size_t)y * w + x0) * 2, v, x0, w);
         }
     }
 }
@@ -2606,24 +2584,11 @@ __global__ void __launch_bounds__(256) k_flow_up(FlowArgs A, float* __restrict__
             const float* rb = src + (uint32_t)(ty.s1 * A.sw) * 2u;
             float v[8];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float2 a0 = *reinterpret_cast<const float2*>(ra + tx[k].s0 * 2);
-                const float2 a1 = *reinterpret_cast<const float2*>(ra + tx[k].s1 * 2);
-                const float2 b0 = *reinterpret_cast<const float2*>(rb + tx[k].s0 * 2);
-                const float2 b1 = *reinterpret_cast<const float2*>(rb + tx[k].s1 * 2);
-                const float t0x = a0.x * tx[k].w0 + a1.x * tx[k].w1, t1x = b0.x * tx[k].w0 + b1.x * tx[k].w1;
-                const float t0y = a0.y * tx[k].w0 + a1.y * tx[k].w1, t1y = b0.y * tx[k].w0 + b1.y * tx[k].w1;
-                v[2 * k] = (t0x * ty.w0 + t1x * ty.w1) * A.g.up;
-                v[2 * k + 1] = (t0y * ty.w0 + t1y * ty.w1) * A.g.up;
-            }
-            float* o = out + ((size_t)t * w * h + (size_t)y * w + x0) * 2;
-            if (x0 + 4 <= w && !(w & 1)) {   // 16-B aligned: x0 % 4 == 0 and rows of an even width
-                *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-                *reinterpret_cast<float4*>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
-            } else {   // the row's last lane, or rows of an odd width (8-B aligned only)
-                const int np = min(4, w - x0);
-                for (int k = 0; k < np; ++k) *reinterpret_cast<float2*>(o + 2 * k) = make_float2(v[2 * k], v[2 * k + 1]);
-            }
+            for (int k = 0; k < 4; ++k)
+                flow_up_px(*reinterpret_cast<const float2*>(ra + tx[k].s0 * 2), *reinterpret_cast<const float2*>(ra + tx[k].s1 * 2),
+                           *reinterpret_cast<const float2*>(rb + tx[k].s0 * 2), *reinterpret_cast<const float2*>(rb + tx[k].s1 * 2),
+                           tx[k], ty, A.g.up, v + 2 * k);
+            flow_up_store(out + ((size_t)t * w * h + (size_t)y * w + x0) * 2, v, x0, w);
         }
     }
 }

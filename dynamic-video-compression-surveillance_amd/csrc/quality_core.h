@@ -10,14 +10,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#ifndef DVC_HD
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define DVC_HD __host__ __device__ __forceinline__
-#else
-#define DVC_HD inline
-#endif
-#endif
+#include "color_core.h"
 
 namespace dvc {
 
@@ -31,11 +24,7 @@ struct QualityCell {
     int s1, s2, ss, s12;
 };
 
-// The project's gray (gray_px in dvc_device.h): OpenCV BGR2GRAY 8U.
-DVC_HD uint32_t quality_luma(uint32_t b, uint32_t g, uint32_t r)
-{
-    return (b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14;
-}
+DVC_HD uint32_t quality_luma(uint32_t b, uint32_t g, uint32_t r) { return gray_px(b, g, r); }   // color_core.h
 
 // One pixel of the reference (a) and of the test frame (b): its squared errors
 // go to sse[0..2] (B, G, R) and sse[3] (luma), its luma to the cell's sums. A

@@ -20,7 +20,7 @@
 #include "../../include/dvc.h"
 #include "host_common.h"
 #include "yuv_kernels.h"
-#include "yuv_px.h"
+#include "px_device.h"
 
 namespace dvc {
 

@@ -366,3 +366,74 @@ def test_fused_i420_outputs_match_oracle(gpu_lib, oracle_lib):
         assert np.array_equal(ov[t - 1].cpu().numpy(), oracle_lib.bgr_to_i420(rov)), f"overlay (I420) at {t}"
         assert np.array_equal(cp[t - 1].cpu().numpy(), oracle_lib.bgr_to_i420(rcp)), f"compressed (I420) at {t}"
     ref.close()
+
+
+_RANDOM_CASES = [
+    # W, H, block, mode, out: the smallest frames that reach every branch of the output kernels
+    (264, 20, 4, "fused", "BGR"),     # two tile columns and rows of the 256x16 front, all blocks full: k_front + k_fix4
+    (264, 20, 4, "fused", "I420"),
+    (264, 20, 4, "unfused", "BGR"),   # the same frames through the one-pass k_out<4>
+    (264, 20, 4, "unfused", "I420"),
+    (262, 18, 4, "fused", "BGR"),     # partial edge blocks and byte output rows: k_out_gen beside the one-pass k_out<4>
+    (72, 24, 8, "fused", "BGR"),      # block 8 is one-pass by default: k_out<8>
+    (72, 24, 8, "fused", "I420"),
+    (72, 24, 8, "fused8", "BGR"),     # DVC_FD_FUSED8=1: the 8x8 front, fixed up by k_out<8, BGR, FIX>
+]
+
+
+@pytest.mark.parametrize("W,H,block,mode,out,fmt", [c + (f,) for c in _RANDOM_CASES
+                                                     for f in (("BGR",) if c[3] == "fused8" else ("BGR", "I420", "NV12"))])
+def test_full_range_random_frames_match_oracle(gpu_lib, oracle_lib, monkeypatch, W, H, block, mode, out, fmt):
+    """Three full-range random frames (saturated colours: every clamp of the
+    YCrCb round trip and of the BT.601 conversions is hit, next to the byte
+    packing) through each output kernel, frames read in place as packed BGR or
+    as 4:2:0 surfaces, BGR or I420 outputs, against the oracle byte for byte."""
+    import ctypes
+    import torch
+    from tests.test_video_io_gpu import _nv12, _oracle_run, _surface
+    if mode == "fused8":   # (the 8x8 front takes BGR frames only)
+        monkeypatch.setenv("DVC_FD_FUSED8", "1")
+    N = gpu_lib._native
+    n = 4
+    rng = np.random.default_rng(1000 * W + 10 * H + block)
+    kw = dict(block_size=block, min_area=20)
+    W4 = (W + 3) & ~3
+    if fmt == "BGR":
+        bgr = rng.integers(0, 256, (n, H, W, 3), dtype=np.uint8)
+        pitch = 3 * W4
+        surf = np.zeros((n, H, pitch), np.uint8)
+        surf[:, :, :3 * W] = bgr.reshape(n, H, 3 * W)
+    else:
+        yuv = rng.integers(0, 256, (n, H * 3 // 2, W), dtype=np.uint8)
+        bgr = np.stack([oracle_lib.yuv420_to_bgr(f) for f in yuv])
+        pitch = W4
+        surf = np.stack([_surface(f if fmt == "I420" else _nv12(f, H, W), H, W, fmt, pitch, H) for f in yuv])
+    outs, st = _oracle_run(oracle_lib, bgr, W, H, **kw)
+    d = torch.from_numpy(surf).cuda()
+    oshape = (n - 1, H, W, 3) if out == "BGR" else (n - 1, H * 3 // 2, W)
+    ov = torch.empty(oshape, dtype=torch.uint8, device="cuda")
+    cp = torch.empty_like(ov)
+    flags = N.DVC_FLAG_DEVICE_PTRS | (N.DVC_FLAG_OUT_I420 if out == "I420" else 0) | \
+        (N.DVC_FLAG_FD_UNFUSED if mode == "unfused" else 0)
+    p = gpu_lib.fd.derive_params(W, H, in_format=fmt, chroma_rows=H if fmt != "BGR" else 0, flags=flags, **kw)
+    p.max_batch = n - 1
+    L = N.lib()
+    h = ctypes.c_void_p()
+    N.check(L.dvc_fd_create(ctypes.byref(p), 0, None, ctypes.byref(h)))
+    try:
+        N.check(L.dvc_fd_prime(h, d[0].data_ptr(), pitch))
+        N.check(L.dvc_fd_step_batch(h, d[1].data_ptr(), pitch, surf[0].nbytes, n - 1, ov.data_ptr(), cp.data_ptr(),
+                                    ov[0].numel()))
+        N.check(L.dvc_fd_sync(h))
+        s = N.FdStats()
+        N.check(L.dvc_fd_get_stats(h, ctypes.byref(s)))
+    finally:
+        L.dvc_fd_destroy(h)
+    ovh, cph = ov.cpu().numpy(), cp.cpu().numpy()
+    conv = (lambda f: f) if out == "BGR" else oracle_lib.bgr_to_i420
+    for t, (ra, rb) in enumerate(outs):
+        assert np.array_equal(ovh[t], conv(ra)), f"overlay differs at frame {t + 1}"
+        assert np.array_equal(cph[t], conv(rb)), f"compressed differs at frame {t + 1}"
+    assert {k: int(getattr(s, k)) for k, _ in s._fields_} == st
+    # noise moves everywhere: blocks that are not static take the YCrCb round trip
+    assert st["static_blocks"] < (n - 1) * -(-W // block) * -(-H // block) // 2
