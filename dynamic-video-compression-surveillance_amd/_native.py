@@ -30,6 +30,7 @@ DVC_FLAG_OF_DIRECT_SUMS = 0x10
 DVC_FLAG_OUT_I420 = 0x20
 DVC_FLAG_FD_UNFUSED = 0x40
 DVC_FLAG_FD_KEPT_PLANE = 0x80
+DVC_FLAG_JPEGD_CAMERA = 0x100
 KTIME_OUT, KTIME_FRONT_FUSED = 0, 1         # dvc_fd_ktime_kernel: which kernel KTIMING timed
 KTIME_FLOW, KTIME_FLOW_SCAN, KTIME_FLOW_SCAN2 = 2, 3, 4   # dvc_of_ktime_kernel: the level-0 flow kernel
 FMT_BGR, FMT_I420, FMT_NV12 = 0, 1, 2      # DVC_FMT_* frame formats (video I/O)
@@ -474,15 +475,18 @@ class JpegDecoder(Handle):
     (H, W, 3) BGR or (H, W) for a single-component stream, the bytes Pillow
     gives. The header (SOI..SOS) is parsed on the host, again only when a
     sample's header bytes differ from the last one's; a stream outside the
-    decoder's set raises DvcError with code DVC_E_UNSUPPORTED."""
+    decoder's set raises DvcError with code DVC_E_UNSUPPORTED. ``camera=True``
+    (DVC_FLAG_JPEGD_CAMERA) widens that set to what cameras and AVI files emit:
+    4:2:2 and 4:4:4 sampling and frames without DHT segments."""
 
     _destroy = "dvc_jpegd_destroy"
 
-    def __init__(self, max_width: int, max_height: int, max_batch: int = 8, device: int = 0):
+    def __init__(self, max_width: int, max_height: int, max_batch: int = 8, device: int = 0, camera: bool = False):
         self.max_batch = max(1, int(max_batch))
         self._in = self._out = None
         self._hdr, self.W, self.H, self.fmt = None, 0, 0, FMT_BGR
-        self._create(lib().dvc_jpegd_create, int(max_width), int(max_height), self.max_batch, int(device), None, 0)
+        self._create(lib().dvc_jpegd_create, int(max_width), int(max_height), self.max_batch, int(device), None,
+                     DVC_FLAG_JPEGD_CAMERA if camera else 0)
 
     def set_header(self, sample: bytes) -> int:
         """Parse ``sample``'s header; returns its length (where the entropy data starts)."""

@@ -47,7 +47,8 @@ int dvc_jpegd_create(int max_width, int max_height, int max_batch, int device, v
     if (max_batch < 0 || max_batch > DVC_MAX_BATCH) return fail(DVC_E_INVALID, "max_batch %d outside 1..%d", max_batch,
                                                                 DVC_MAX_BATCH);
     const size_t yw = up(max_width, 16), yh = up(max_height, 16);
-    const size_t ncoef = yw * yh * 3 / 2;                                        // 4:2:0, the larger of the two layouts
+    // 4:2:0, the larger of the two layouts; a camera handle's largest is 4:4:4's three full planes
+    const size_t ncoef = (flags & DVC_FLAG_JPEGD_CAMERA) ? yw * yh * 3 : yw * yh * 3 / 2;
     const size_t nmark = up(max_width, 8) / 8 * (up(max_height, 8) / 8);         // one MCU per segment, one component
     if (ncoef * 2 > 0x7fffffffull) return fail(DVC_E_UNSUPPORTED, "largest frame %dx%d too large", max_width, max_height);
     dvc_jpegd* h = new dvc_jpegd();
@@ -89,7 +90,7 @@ int dvc_jpegd_set_header(dvc_jpegd* h, const uint8_t* hdr, size_t n, size_t* hea
     if (!h || !hdr) return fail(DVC_E_INVALID, "NULL argument");
     dvc::JpegdHeader parsed;
     const char* why = "";
-    const int rc = dvc::jpegd_parse_header(hdr, n, &parsed, &why);
+    const int rc = dvc::jpegd_parse_header(hdr, n, &parsed, &why, (h->flags & DVC_FLAG_JPEGD_CAMERA) != 0);
     if (rc != dvc::kJpegdOk) return fail(rc, "JPEG header: %s", why);
     if (parsed.g.W > h->max_w || parsed.g.H > h->max_h)
         return fail(DVC_E_INVALID, "frame %dx%d exceeds the handle's %dx%d", parsed.g.W, parsed.g.H, h->max_w, h->max_h);

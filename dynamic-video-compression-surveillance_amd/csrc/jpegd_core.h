@@ -35,18 +35,22 @@ struct JpegdTables {
     uint8_t pad_[2];
 };
 
-// One stream's geometry. An MCU is 16x16 pixels in six blocks (Y00 Y01 Y10 Y11
-// Cb Cr) or, for a single component, one 8x8 block; a restart segment is `ri`
-// MCUs in raster order (the last may be shorter).
+// One stream's geometry. A single component's MCU is one 8x8 block. A colour
+// MCU is 8 hs x 8 vs pixels, (hs, vs) the luma sampling factors: 2x2 (4:2:0),
+// and for a camera handle 2x1 (4:2:2) and 1x1 (4:4:4); its hs * vs + 2 blocks
+// are the luma blocks in raster order inside the MCU (Y00 Y01 Y10 Y11), then
+// Cb, Cr. A restart segment is `ri` MCUs in raster order (the last may be
+// shorter). The real chroma size is ceil(W / hs) x ceil(H / vs).
 struct JpegdGeom {
     int W, H;
     int gray;
     int mcus_x, mcus_y, mcus;
     int ri;       // MCUs per segment (the whole frame when the stream has no DRI)
     int nseg;
-    int bpm;      // blocks per MCU: 6 or 1
+    int bpm;      // blocks per MCU: hs * vs + 2, or 1
     int yw, yh;   // the MCU-padded luma plane
-    int cw, ch;   // the MCU-padded chroma planes (0 when gray)
+    int cw, ch;   // the MCU-padded chroma planes, 8 mcus_x x 8 mcus_y (0 when gray)
+    int hs, vs;   // luma sampling factors (1, 1 when gray)
 };
 
 // Canonical tables from a DHT's BITS (16 counts) and HUFFVAL. False when the
@@ -170,17 +174,22 @@ DVC_HD bool jpegd_receive(JpegdBits& b, int s, int* out)
 
 // One restart segment: `nmcu` MCUs of entropy data in p[0, len) -> int16 levels,
 // natural order, 64 per block, blocks in scan order at `coef` (zero on entry).
-// Every read is inside p[0, len) and every store inside coef[0, nmcu * bpm * 64).
-// Returns 0, or kJpegdDamaged at the first invalid code, run past coefficient 63
-// or read past the data.
-DVC_HD int jpegd_segment(const uint8_t* p, uint32_t len, int nmcu, int gray, const JpegdTables* t, int16_t* coef)
+// `bpm` is the layout (JpegdGeom::bpm): 1 for a single component, otherwise the
+// MCU's bpm - 2 luma blocks come first, then Cb and Cr. Every read is inside
+// p[0, len) and every store inside coef[0, nmcu * bpm * 64). Returns 0, or
+// kJpegdDamaged at the first invalid code, run past coefficient 63 or read past
+// the data. CAMERA false is the text for the two layouts of a default handle
+// (bpm 1 and 6), which keeps its code; true takes any bpm.
+template <bool CAMERA>
+DVC_HD int jpegd_segment_t(const uint8_t* p, uint32_t len, int nmcu, int layout, const JpegdTables* t, int16_t* coef)
 {
     JpegdBits b{p, len, 0u, 0ull, 0};
     int pred[3] = {0, 0, 0};
-    const int bpm = gray ? 1 : 6;
+    const int bpm = CAMERA ? layout : (layout == 1 ? 1 : 6);
+    const int nluma = bpm == 1 ? 1 : bpm - 2;
     for (int m = 0; m < nmcu; ++m) {
         for (int j = 0; j < bpm; ++j) {
-            const int c = j < 4 ? 0 : j - 3;
+            const int c = CAMERA ? (j < nluma ? 0 : j - nluma + 1) : (j < 4 ? 0 : j - 3);
             const JpegdHuff* dc = &t->dc[t->dc_sel[c] & 1];
             const JpegdHuff* ac = &t->ac[t->ac_sel[c] & 1];
             int16_t* blk = coef + ((size_t)m * bpm + j) * 64;
@@ -214,6 +223,12 @@ DVC_HD int jpegd_segment(const uint8_t* p, uint32_t len, int nmcu, int gray, con
         }
     }
     return 0;
+}
+
+DVC_HD int jpegd_segment(const uint8_t* p, uint32_t len, int nmcu, int bpm, const JpegdTables* t, int16_t* coef)
+{
+    if (bpm == 1 || bpm == 6) return jpegd_segment_t<false>(p, len, nmcu, bpm, t, coef);
+    return jpegd_segment_t<true>(p, len, nmcu, bpm, t, coef);
 }
 
 // libjpeg's slow-integer 8-point inverse DCT pass (jidctint): out[i] = (x + rnd)
@@ -289,6 +304,17 @@ DVC_HD int jpegd_chroma_at(const uint8_t* p, size_t cw, int dw, int dh, int x, i
     const int s = jpegd_vsum(p, cw, dh, r, cx, bottom);
     if (x & 1) return (3 * s + jpegd_vsum(p, cw, dh, r, cx + 1 < dw ? cx + 1 : dw - 1, bottom) + 7) >> 4;
     return (3 * s + jpegd_vsum(p, cw, dh, r, cx > 0 ? cx - 1 : 0, bottom) + 8) >> 4;
+}
+
+// 4:2:2 (camera handles): the upsampled chroma sample at output pixel (x, y). No
+// vertical step; along the row 3/4 of the nearer sample and 1/4 of the farther.
+DVC_HD int jpegd_chroma_at_h2v1(const uint8_t* p, size_t cw, int dw, int x, int y)
+{
+    const int cx = x >> 1;
+    const uint8_t* row = p + (size_t)y * cw;
+    if (dw <= 2) return row[cx];
+    if (x & 1) return (3 * (int)row[cx] + (int)row[cx + 1 < dw ? cx + 1 : dw - 1] + 2) >> 2;
+    return (3 * (int)row[cx] + (int)row[cx > 0 ? cx - 1 : 0] + 1) >> 2;
 }
 
 // Y, Cb, Cr (0..255) -> bgr[3].

@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <string.h>
 
+#include "jpeg_std_tables.h"
 #include "jpegd_core.h"
 
 namespace dvc {
@@ -26,8 +27,12 @@ struct JpegdHeader {
 // Parses d[0, n). On success fills *out and returns kJpegdOk; otherwise returns
 // kJpegdInvalid (not a header, cut short, inconsistent) or kJpegdUnsupported (a
 // JPEG this decoder does not take) with *why naming the reason and *out
-// unspecified. Nothing outside d[0, n) is read.
-inline int jpegd_parse_header(const uint8_t* d, size_t n, JpegdHeader* out, const char** why)
+// unspecified. Nothing outside d[0, n) is read. `camera` (DVC_FLAG_JPEGD_CAMERA)
+// widens the set: 4:2:2 (2x1) and 4:4:4 luma factors, and a scan whose Huffman
+// tables no DHT defined means the Annex K ones; it refuses RGB-coded streams by
+// libjpeg's rule (no JFIF APP0 and an Adobe APP14 with transform 0, or neither
+// and the component ids 'R', 'G', 'B').
+inline int jpegd_parse_header(const uint8_t* d, size_t n, JpegdHeader* out, const char** why, bool camera = false)
 {
     const char* dummy;
     if (!why) why = &dummy;
@@ -39,7 +44,9 @@ inline int jpegd_parse_header(const uint8_t* d, size_t n, JpegdHeader* out, cons
     JpegdHeader& o = *out;
     memset(&o, 0, sizeof(o));
     memcpy(o.t.nat, kJpegdNat, 64);
-    int nc = 0, dri = 0, cid[3] = {0, 0, 0}, cq[3] = {0, 0, 0};
+    int nc = 0, dri = 0, cid[3] = {0, 0, 0}, cq[3] = {0, 0, 0}, hs = 1, vs = 1;
+    bool jfif = false, adobe = false;
+    int adobe_transform = 0;
     size_t p = 2;
     for (;;) {
         if (p + 4 > n) return *why = "header cut short", kJpegdInvalid;
@@ -54,6 +61,11 @@ inline int jpegd_parse_header(const uint8_t* d, size_t n, JpegdHeader* out, cons
         const uint8_t* b = d + p + 4;
         const size_t bl = ln - 2;
         p += 2 + ln;
+        if (m == 0xe0 && bl >= 5 && memcmp(b, "JFIF", 5) == 0) jfif = true;
+        if (m == 0xee && bl >= 12 && memcmp(b, "Adobe", 5) == 0) {
+            adobe = true;
+            adobe_transform = b[11];
+        }
         if ((m >= 0xe0 && m <= 0xef) || m == 0xfe) continue;   // APPn, COM
         if (m == 0xdb) {
             size_t i = 0;
@@ -95,8 +107,15 @@ inline int jpegd_parse_header(const uint8_t* d, size_t n, JpegdHeader* out, cons
                 cq[c] = b[8 + 3 * c];
                 if (cq[c] > 3) return *why = "bad SOF", kJpegdInvalid;
                 // (a single component's factors do not matter: its scan is not interleaved)
-                if (nc == 3 && hv != (c == 0 ? 0x22 : 0x11))
-                    return *why = "sampling other than 4:2:0", kJpegdUnsupported;
+                if (nc == 3 && hv != (c == 0 ? 0x22 : 0x11)) {
+                    if (!camera) return *why = "sampling other than 4:2:0", kJpegdUnsupported;
+                    if (c != 0 || (hv != 0x21 && hv != 0x11))
+                        return *why = "sampling other than 4:2:0, 4:2:2 (2x1) and 4:4:4", kJpegdUnsupported;
+                }
+                if (nc == 3 && c == 0) {
+                    hs = hv >> 4;
+                    vs = hv & 15;
+                }
             }
             have_sof = true;
         } else if (m == 0xc1 || m == 0xc2 || m == 0xc3 || (m >= 0xc5 && m <= 0xcf && m != 0xc8 && m != 0xcc)) {
@@ -114,7 +133,17 @@ inline int jpegd_parse_header(const uint8_t* d, size_t n, JpegdHeader* out, cons
                 if (b[1 + 2 * c] != cid[c]) return *why = "scan components out of order", kJpegdUnsupported;
                 const int td = b[2 + 2 * c] >> 4, ta = b[2 + 2 * c] & 15;
                 if (td > 1 || ta > 1) return *why = "more than two Huffman tables of a class", kJpegdUnsupported;
-                if (!have_h[0][td] || !have_h[1][ta]) return *why = "scan names a missing Huffman table", kJpegdInvalid;
+                if (!have_h[0][td] || !have_h[1][ta]) {
+                    if (!camera) return *why = "scan names a missing Huffman table", kJpegdInvalid;
+                    for (int cls = 0; cls < 2; ++cls) {   // the Annex K table of the slot
+                        const int id = cls ? ta : td;
+                        if (have_h[cls][id]) continue;
+                        const JpegStdTable s = jpeg_std_table(cls, id);
+                        if (!jpegd_build_huff(s.bits, s.vals, s.nvals, cls ? &o.t.ac[id] : &o.t.dc[id]))
+                            return *why = "bad DHT", kJpegdInvalid;
+                        have_h[cls][id] = true;
+                    }
+                }
                 if (!have_q[cq[c]]) return *why = "frame names a missing quantiser table", kJpegdInvalid;
                 o.t.dc_sel[c] = (uint8_t)td;
                 o.t.ac_sel[c] = (uint8_t)ta;
@@ -122,6 +151,9 @@ inline int jpegd_parse_header(const uint8_t* d, size_t n, JpegdHeader* out, cons
             }
             if (b[1 + 2 * nc] != 0 || b[2 + 2 * nc] != 63 || b[3 + 2 * nc] != 0)
                 return *why = "not a sequential scan", kJpegdUnsupported;
+            if (camera && nc == 3 && !jfif &&
+                (adobe ? adobe_transform == 0 : (cid[0] == 'R' && cid[1] == 'G' && cid[2] == 'B')))
+                return *why = "RGB-coded components", kJpegdUnsupported;
             break;
         } else {
             return *why = "unexpected marker", kJpegdInvalid;
@@ -129,15 +161,17 @@ inline int jpegd_parse_header(const uint8_t* d, size_t n, JpegdHeader* out, cons
     }
     JpegdGeom& g = o.g;
     g.gray = nc == 1;
-    const int mpx = g.gray ? 8 : 16;
-    g.mcus_x = (g.W + mpx - 1) / mpx;
-    g.mcus_y = (g.H + mpx - 1) / mpx;
+    g.hs = g.gray ? 1 : hs;
+    g.vs = g.gray ? 1 : vs;
+    const int mw = 8 * g.hs, mh = 8 * g.vs;
+    g.mcus_x = (g.W + mw - 1) / mw;
+    g.mcus_y = (g.H + mh - 1) / mh;
     g.mcus = g.mcus_x * g.mcus_y;
     g.ri = dri ? (dri < g.mcus ? dri : g.mcus) : g.mcus;
     g.nseg = (g.mcus + g.ri - 1) / g.ri;
-    g.bpm = g.gray ? 1 : 6;
-    g.yw = g.mcus_x * mpx;
-    g.yh = g.mcus_y * mpx;
+    g.bpm = g.gray ? 1 : g.hs * g.vs + 2;
+    g.yw = g.mcus_x * mw;
+    g.yh = g.mcus_y * mh;
     g.cw = g.gray ? 0 : g.mcus_x * 8;
     g.ch = g.gray ? 0 : g.mcus_y * 8;
     o.length = p;

@@ -6,8 +6,10 @@
 //   k_jpegd_count  RSTn markers in each chunk of every frame
 //   k_jpegd_index  their positions, in order; a wrong count damages the frame
 //   k_jpegd_huff   one lane per restart segment: Huffman symbols -> int16 levels
-//   k_jpegd_idct   dequantise, integer IDCT in LDS -> Y, Cb, Cr planes (chroma at half size)
+//   k_jpegd_idct   dequantise, integer IDCT in LDS -> Y, Cb, Cr planes (chroma at its coded size)
 //   k_jpegd_out    fancy chroma upsampling, YCbCr -> BGR (or the luma plane) -> the caller's rows
+// k_jpegd_idct and k_jpegd_out are instantiated per layout (JpegdLayout): one
+// component, 4:2:0, and a camera handle's 4:2:2 and 4:4:4.
 //   k_jpegd_err    the batch's first damaged frame -> the handle's sticky word
 //
 // All integer-exact; every store is an ordinary vector store.
@@ -21,6 +23,9 @@ namespace {
 
 constexpr int kHuffMaxLanes = 16;       // the most decoding lanes of a k_jpegd_huff workgroup (one wave)
 constexpr long long kHuffWaves = 2048;   // workgroups to aim for: two waves on each of the 1024 SIMDs
+
+// A stream's layout, the template parameter of k_jpegd_idct and k_jpegd_out.
+enum JpegdLayout { kLayGray = 0, kLay420 = 1, kLay422 = 2, kLay444 = 3 };
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane)
 {
@@ -131,7 +136,9 @@ __global__ __launch_bounds__(256) void k_jpegd_index(const uint8_t* __restrict__
 // whose threads first copy the tables into LDS. Lanes of a wave decode different
 // data, so they diverge at every branch: the fewer share a wave, the less each
 // waits for the others, and the launch picks one lane a wave until there are
-// waves enough to fill the machine.
+// waves enough to fill the machine. CAMERA: a 4:2:2 or 4:4:4 stream (jpegd_segment_t);
+// the layouts of a default handle run the instantiation they always ran.
+template <bool CAMERA>
 __global__ __launch_bounds__(64) void k_jpegd_huff(const uint8_t* __restrict__ data, size_t stride,
                                                    const uint32_t* __restrict__ sizes, int n, JpegdGeom g,
                                                    const JpegdTables* __restrict__ tab, int lanes,
@@ -161,20 +168,23 @@ __global__ __launch_bounds__(64) void k_jpegd_huff(const uint8_t* __restrict__ d
     }
     const int m0 = s * g.ri, nmcu = min(g.ri, g.mcus - m0);
     int16_t* dst = coef + ((size_t)f * g.mcus + m0) * g.bpm * 64;
-    const int rc = jpegd_segment(data + (size_t)f * stride + start, end - start, nmcu, g.gray, &s_tab, dst);
+    const int rc = jpegd_segment_t<CAMERA>(data + (size_t)f * stride + start, end - start, nmcu, g.bpm, &s_tab, dst);
     if (rc != 0) atomicMin(&status[f], rc);
 }
 
 // ---- k_jpegd_idct -----------------------------------------------------------------
-// 256 threads = 4 waves, one work unit each: an MCU's six blocks (colour) or four
-// consecutive blocks (one component). A lane takes column i8 of block blk, then
-// its row i8; the pass between them goes through LDS.
-template <bool GRAY>
+// 256 threads = 4 waves, one work unit each: an MCU's six blocks (4:2:0), four
+// consecutive blocks (one component), two MCUs' eight blocks (4:2:2) or eight
+// consecutive scan-order blocks (4:4:4: block b is plane b % 3 of MCU b / 3, so
+// an MCU may straddle waves and workgroups). A lane takes column i8 of block
+// blk, then its row i8; the pass between them goes through LDS.
+template <int L>
 __global__ __launch_bounds__(256) void k_jpegd_idct(JpegdGeom g, const JpegdTables* __restrict__ tab,
                                                     const int16_t* __restrict__ coef, uint8_t* __restrict__ planes,
                                                     const int32_t* __restrict__ status)
 {
-    constexpr int NB = GRAY ? 4 : 6;
+    constexpr bool GRAY = L == kLayGray;
+    constexpr int NB = L == kLayGray ? 4 : (L == kLay420 ? 6 : 8);
     __shared__ int32_t s_ws[4][NB * 64];
     __shared__ uint16_t s_q[3 * 64];
     const int f = blockIdx.y;
@@ -187,7 +197,10 @@ __global__ __launch_bounds__(256) void k_jpegd_idct(JpegdGeom g, const JpegdTabl
     const int b = unit * NB + blk;   // the frame's block in scan order
     const bool live = blk < NB && b < nblocks;
     __syncthreads();
-    const int comp = GRAY ? 0 : (blk < 4 ? 0 : blk - 3);
+    // 4:2:2, 4:4:4: the block's MCU and its place in it
+    const int mcu = L == kLay422 ? b >> 2 : (L == kLay444 ? b / 3 : 0);
+    const int jb = L == kLay422 ? b & 3 : (L == kLay444 ? b - 3 * mcu : 0);
+    const int comp = GRAY ? 0 : (L == kLay420 ? (blk < 4 ? 0 : blk - 3) : (L == kLay422 ? (jb < 2 ? 0 : jb - 1) : jb));
     if (live) {
         const int16_t* lv = coef + ((size_t)f * nblocks + b) * 64;
         const uint16_t* q = s_q + comp * 64;
@@ -212,12 +225,19 @@ __global__ __launch_bounds__(256) void k_jpegd_idct(JpegdGeom g, const JpegdTabl
     if (GRAY) {
         const int my = b / g.mcus_x, mx = b - my * g.mcus_x;
         dst = fp + (size_t)(my * 8 + i8) * g.yw + mx * 8;
-    } else {
+    } else if (L == kLay420) {
         const int my = unit / g.mcus_x, mx = unit - my * g.mcus_x;
         if (blk < 4)
             dst = fp + (size_t)(my * 16 + (blk >> 1) * 8 + i8) * g.yw + mx * 16 + (blk & 1) * 8;
         else
             dst = fp + (size_t)g.yw * g.yh + (size_t)(blk - 4) * g.cw * g.ch + (size_t)(my * 8 + i8) * g.cw + mx * 8;
+    } else {
+        // mcu < g.mcus since b < nblocks: the row is inside the plane's mcus_y * 8 rows
+        const int my = mcu / g.mcus_x, mx = mcu - my * g.mcus_x;
+        if (comp == 0)
+            dst = fp + (size_t)(my * 8 + i8) * g.yw + (L == kLay422 ? mx * 16 + jb * 8 : mx * 8);
+        else
+            dst = fp + (size_t)g.yw * g.yh + (size_t)(comp - 1) * g.cw * g.ch + (size_t)(my * 8 + i8) * g.cw + mx * 8;
     }
     uint32_t* d32 = reinterpret_cast<uint32_t*>(dst);   // plane pitches and block columns are multiples of 8
     d32[0] = w[0];
@@ -225,11 +245,30 @@ __global__ __launch_bounds__(256) void k_jpegd_idct(JpegdGeom g, const JpegdTabl
 }
 
 // ---- k_jpegd_out ------------------------------------------------------------------
-// A lane per 4 output pixels x 2 rows (one chroma row): the upsampling rules from
-// the chroma planes with their true neighbours, the colour conversion, and three
-// dword stores a row where the rows are 4-byte aligned. A damaged frame's slot is
-// left untouched.
-template <bool GRAY>
+// A lane per 4 output pixels x 2 rows (4:2:0: one chroma row): the upsampling
+// rules from the chroma planes with their true neighbours, the colour conversion,
+// and three dword stores a row where the rows are 4-byte aligned. 4:2:2 upsamples
+// along the row only; 4:4:4 takes the chroma samples as they are (a dword of each
+// plane a row: 3 B/px read, 3 B/px written). A damaged frame's slot is left
+// untouched.
+__device__ __forceinline__ void jpegd_store_bgr4(uint8_t* row, uint32_t yv, const int* cb, const int* cr, bool dwords,
+                                                 int nx)
+{
+    uint8_t px[12];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) jpegd_bgr((int)((yv >> (8 * i)) & 0xffu), cb[i], cr[i], px + 3 * i);
+    if (dwords) {
+        uint32_t* d32 = reinterpret_cast<uint32_t*>(row);
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+            d32[w] = (uint32_t)px[4 * w] | (uint32_t)px[4 * w + 1] << 8 | (uint32_t)px[4 * w + 2] << 16 |
+                     (uint32_t)px[4 * w + 3] << 24;
+    } else {
+        for (int i = 0; i < 3 * nx; ++i) row[i] = px[i];
+    }
+}
+
+template <int L>
 __global__ __launch_bounds__(256) void k_jpegd_out(JpegdGeom g, const uint8_t* __restrict__ planes,
                                                    uint8_t* __restrict__ out, size_t pitch, size_t fstride, int aligned,
                                                    const int32_t* __restrict__ status)
@@ -242,6 +281,53 @@ __global__ __launch_bounds__(256) void k_jpegd_out(JpegdGeom g, const uint8_t* _
     const uint8_t* fp = planes + (size_t)f * ((size_t)g.yw * g.yh + 2 * (size_t)g.cw * g.ch);
     uint8_t* o = out + (size_t)f * fstride;
     const int rows = min(2, g.H - y0), nx = min(4, g.W - x0);
+    if constexpr (L == kLay444) {
+        const size_t psz = (size_t)g.yw * g.yh;   // the three planes are one size
+        for (int dy = 0; dy < rows; ++dy) {
+            // x0 is a multiple of 4 below W <= yw, yw a multiple of 8: the dword is inside the row
+            const uint8_t* src = fp + (size_t)(y0 + dy) * g.yw + x0;
+            const uint32_t yv = *reinterpret_cast<const uint32_t*>(src);
+            const uint32_t bv = *reinterpret_cast<const uint32_t*>(src + psz);
+            const uint32_t rv = *reinterpret_cast<const uint32_t*>(src + 2 * psz);
+            int cb[4], cr[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                cb[i] = (int)((bv >> (8 * i)) & 0xffu);
+                cr[i] = (int)((rv >> (8 * i)) & 0xffu);
+            }
+            jpegd_store_bgr4(o + (size_t)(y0 + dy) * pitch + 3 * (size_t)x0, yv, cb, cr, aligned && nx == 4, nx);
+        }
+        return;
+    }
+    if constexpr (L == kLay422) {
+        const int dw = (g.W + 1) >> 1;
+        const uint8_t* cp[2] = {fp + (size_t)g.yw * g.yh, fp + (size_t)g.yw * g.yh + (size_t)g.cw * g.ch};
+        // chroma columns 2j - 1 .. 2j + 2, clamped to the real width (2j < dw since x0 < W)
+        const int col[4] = {max(2 * j - 1, 0), 2 * j, min(2 * j + 1, dw - 1), min(2 * j + 2, dw - 1)};
+        for (int dy = 0; dy < rows; ++dy) {
+            int up[2][4];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const uint8_t* crow = cp[c] + (size_t)(y0 + dy) * g.cw;   // chroma rows are luma rows
+                int p[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) p[i] = (int)crow[col[i]];
+                if (dw <= 2) {
+                    up[c][0] = up[c][1] = p[1];
+                    up[c][2] = up[c][3] = p[2];
+                } else {
+                    up[c][0] = (3 * p[1] + p[0] + 1) >> 2;
+                    up[c][1] = (3 * p[1] + p[2] + 2) >> 2;
+                    up[c][2] = (3 * p[2] + p[1] + 1) >> 2;
+                    up[c][3] = (3 * p[2] + p[3] + 2) >> 2;
+                }
+            }
+            const uint32_t yv = *reinterpret_cast<const uint32_t*>(fp + (size_t)(y0 + dy) * g.yw + x0);
+            jpegd_store_bgr4(o + (size_t)(y0 + dy) * pitch + 3 * (size_t)x0, yv, up[0], up[1], aligned && nx == 4, nx);
+        }
+        return;
+    }
+    constexpr bool GRAY = L == kLayGray;
     if (GRAY) {
         for (int dy = 0; dy < rows; ++dy) {
             const uint32_t v = *reinterpret_cast<const uint32_t*>(fp + (size_t)(y0 + dy) * g.yw + x0);
@@ -328,21 +414,39 @@ hipError_t jpegd_launch(const uint8_t* data, size_t stride, const uint32_t* size
                        b.chunkcnt, b.markpos, status);
     const long long segs = (long long)n * g.nseg;
     const int lanes = (int)std::min<long long>(kHuffMaxLanes, std::max<long long>(1, segs / kHuffWaves));
-    hipLaunchKernelGGL(k_jpegd_huff, dim3((unsigned)((segs + lanes - 1) / lanes)), dim3(64), 0, st, data, stride, sizes, n,
-                       g, tab, lanes, b.markpos, b.coef, status);
+    if (g.bpm == 1 || g.bpm == 6)
+        hipLaunchKernelGGL(k_jpegd_huff<false>, dim3((unsigned)((segs + lanes - 1) / lanes)), dim3(64), 0, st, data, stride,
+                           sizes, n, g, tab, lanes, b.markpos, b.coef, status);
+    else
+        hipLaunchKernelGGL(k_jpegd_huff<true>, dim3((unsigned)((segs + lanes - 1) / lanes)), dim3(64), 0, st, data, stride,
+                           sizes, n, g, tab, lanes, b.markpos, b.coef, status);
     const int aligned = pitch % 4 == 0 && ((uintptr_t)out & 3) == 0 && (n <= 1 || fstride % 4 == 0);
     const dim3 ogrid((unsigned)(((g.W + 3) / 4 + 63) / 64), (unsigned)(((g.H + 1) / 2 + 3) / 4), (unsigned)n);
     if (g.gray) {
         const int units = (g.mcus + 3) / 4;
-        hipLaunchKernelGGL(k_jpegd_idct<true>, dim3((unsigned)((units + 3) / 4), (unsigned)n), dim3(256), 0, st, g, tab,
-                           b.coef, b.planes, status);
-        hipLaunchKernelGGL(k_jpegd_out<true>, ogrid, dim3(64, 4), 0, st, g, b.planes, out, pitch, fstride, aligned,
+        hipLaunchKernelGGL(k_jpegd_idct<kLayGray>, dim3((unsigned)((units + 3) / 4), (unsigned)n), dim3(256), 0, st, g,
+                           tab, b.coef, b.planes, status);
+        hipLaunchKernelGGL(k_jpegd_out<kLayGray>, ogrid, dim3(64, 4), 0, st, g, b.planes, out, pitch, fstride, aligned,
+                           status);
+    } else if (g.hs == 2 && g.vs == 2) {
+        hipLaunchKernelGGL(k_jpegd_idct<kLay420>, dim3((unsigned)((g.mcus + 3) / 4), (unsigned)n), dim3(256), 0, st, g,
+                           tab, b.coef, b.planes, status);
+        hipLaunchKernelGGL(k_jpegd_out<kLay420>, ogrid, dim3(64, 4), 0, st, g, b.planes, out, pitch, fstride, aligned,
+                           status);
+    } else if (g.hs == 2 && g.vs == 1) {   // two MCUs a wave
+        const int units = (g.mcus + 1) / 2;
+        hipLaunchKernelGGL(k_jpegd_idct<kLay422>, dim3((unsigned)((units + 3) / 4), (unsigned)n), dim3(256), 0, st, g,
+                           tab, b.coef, b.planes, status);
+        hipLaunchKernelGGL(k_jpegd_out<kLay422>, ogrid, dim3(64, 4), 0, st, g, b.planes, out, pitch, fstride, aligned,
+                           status);
+    } else if (g.hs == 1 && g.vs == 1) {   // eight scan-order blocks a wave
+        const int units = (3 * g.mcus + 7) / 8;
+        hipLaunchKernelGGL(k_jpegd_idct<kLay444>, dim3((unsigned)((units + 3) / 4), (unsigned)n), dim3(256), 0, st, g,
+                           tab, b.coef, b.planes, status);
+        hipLaunchKernelGGL(k_jpegd_out<kLay444>, ogrid, dim3(64, 4), 0, st, g, b.planes, out, pitch, fstride, aligned,
                            status);
     } else {
-        hipLaunchKernelGGL(k_jpegd_idct<false>, dim3((unsigned)((g.mcus + 3) / 4), (unsigned)n), dim3(256), 0, st, g, tab,
-                           b.coef, b.planes, status);
-        hipLaunchKernelGGL(k_jpegd_out<false>, ogrid, dim3(64, 4), 0, st, g, b.planes, out, pitch, fstride, aligned,
-                           status);
+        return hipErrorInvalidValue;   // (the header parser accepts no other layout)
     }
     hipLaunchKernelGGL(k_jpegd_err, dim3(1), dim3(1), 0, st, status, n, b.first_err);
     return hipGetLastError();

@@ -29,7 +29,13 @@ the accelerated path. Here:
 * such an ``.mp4`` is readable again (``Mp4MjpegReader``: the samples demuxed
   here, decoded in batches on the GPU by ``dvc_jpegd_decode``, or by Pillow —
   the same bytes; ``DVC_MJPEG_DECODE=auto|gpu|pillow``) — the OF driver's
-  second pass and ``performance_analysis`` read the files the first pass wrote.
+  second pass and ``performance_analysis`` read the files the first pass wrote;
+* camera Motion-JPEG is readable without OpenCV: ``*.avi`` (RIFF AVI with an
+  ``MJPG`` video stream, :class:`AviMjpegReader`) and raw ``*.mjpeg`` /
+  ``*.mjpg`` streams (JPEG images end to end, :class:`MjpegStreamReader`; the
+  file carries no frame rate: ``DVC_MJPEG_FPS``, default 25). Both decode on a
+  camera handle (``JpegDecoder(camera=True)``: 4:2:0, 4:2:2, 4:4:4, frames
+  without DHT segments) and obey ``DVC_MJPEG_DECODE`` as above.
 """
 from __future__ import annotations
 
@@ -535,6 +541,204 @@ class Mp4MjpegReader:
             self._dec = None
 
 
+class _CameraMjpegReader(Mp4MjpegReader):
+    """What :class:`AviMjpegReader` and :class:`MjpegStreamReader` share: the
+    surface and the decoding of :class:`Mp4MjpegReader` over their own sample
+    list, on a camera handle (``JpegDecoder(camera=True)``). A sample that does
+    not decode, or whose frame size differs from the first sample's, ends the
+    stream."""
+
+    def __init__(self, path: str, device: int = 0, batch: int = 8):
+        self._shape = None
+        super().__init__(path, device, batch)
+
+    def _fill(self) -> None:
+        if self._dec is None:
+            from . import _native as N
+            self._dec = N.JpegDecoder(self.W, self.H, self._batch, self._device, camera=True)
+        super()._fill()
+
+    def read(self):
+        try:
+            ok, f = super().read()
+        except (OSError, SyntaxError, ValueError):   # Pillow on a sample it cannot decode
+            ok, f = False, None
+        if ok and self._shape is None:
+            self._shape = f.shape[:2]
+        if not ok or f.shape[:2] != self._shape:
+            self._ready, self._i = [], len(self.samples)
+            return False, None
+        return True, f
+
+
+def jpeg_image_end(buf, start: int) -> int:
+    """The end (one past EOI) of the JPEG image whose SOI is at ``buf[start]``, or
+    -1 when it does not parse. The marker segments from SOI to SOS are walked by
+    their lengths (an APP1 thumbnail holds SOI and EOI of its own); the entropy
+    data is then scanned for the first 0xFF whose next byte is not 0x00 (a stuffed
+    byte), 0xFF (fill) or 0xD0..0xD7 (a restart marker): that marker must be EOI."""
+    n, p = len(buf), start + 2
+    if n < start + 4 or buf[start] != 0xFF or buf[start + 1] != 0xD8:
+        return -1
+    while True:
+        if p + 4 > n or buf[p] != 0xFF:
+            return -1
+        m = buf[p + 1]
+        if m == 0xFF:   # fill byte
+            p += 1
+            continue
+        if m in (0x00, 0x01, 0xD8, 0xD9) or 0xD0 <= m <= 0xD7:
+            return -1   # no marker segment: not a header this reader can walk
+        ln = (int(buf[p + 2]) << 8) | int(buf[p + 3])
+        if ln < 2 or p + 2 + ln > n:
+            return -1
+        p += 2 + ln
+        if m == 0xDA:
+            break
+    while p < n:
+        w = np.frombuffer(buf, np.uint8, min(n - p, 1 << 20), p) if not isinstance(buf, np.ndarray) \
+            else buf[p:p + (1 << 20)]
+        nxt = w[1:]
+        hit = np.flatnonzero((w[:-1] == 0xFF) & (nxt != 0x00) & (nxt != 0xFF) & ((nxt & 0xF8) != 0xD0))
+        if len(hit):
+            i = p + int(hit[0])
+            return i + 2 if buf[i + 1] == 0xD9 else -1
+        if len(w) < 2:
+            break
+        p += len(w) - 1   # the window's last byte starts the next one
+    return -1
+
+
+class MjpegStreamReader(_CameraMjpegReader):
+    """cv2.VideoCapture-like reader of a raw Motion-JPEG stream (``.mjpeg``,
+    ``.mjpg``: what ``ffmpeg -f mjpeg`` writes and an IP camera's HTTP stream
+    carries): JPEG images end to end, split by :func:`jpeg_image_end`. Bytes
+    between images are skipped up to the next SOI; an image that does not parse
+    (a cut last one) ends the stream. The size is the first image's; the file
+    carries no frame rate: ``DVC_MJPEG_FPS`` (default 25) gives it."""
+
+    def _parse(self, path):
+        self.fps = float(os.environ.get("DVC_MJPEG_FPS", 25))
+        if not self.fps > 0:
+            raise ValueError("DVC_MJPEG_FPS")
+        self._fp = open(path, "rb")
+        mm = np.memmap(path, np.uint8, mode="r")
+        p, self.samples = 0, []
+        while True:
+            p = _next_soi(mm, p)
+            if p < 0:
+                break
+            end = jpeg_image_end(mm, p)
+            if end < 0:
+                break
+            self.samples.append((p, end - p))
+            p = end
+        if not self.samples:
+            raise ValueError("no JPEG image")
+        self.W, self.H = _jpeg_size(bytes(mm[self.samples[0][0]:sum(self.samples[0])]))
+        del mm
+
+
+def _next_soi(buf, p: int) -> int:
+    """The first SOI marker at or after ``buf[p]`` (outside an image), or -1."""
+    while p + 2 <= len(buf):
+        w = buf[p:p + (1 << 20)]
+        hit = np.flatnonzero((w[:-1] == 0xFF) & (w[1:] == 0xD8))
+        if len(hit):
+            return p + int(hit[0])
+        p += len(w) - 1
+    return -1
+
+
+def _jpeg_size(jpg: bytes):
+    """(W, H) of a JPEG image, from its first SOFn segment."""
+    p = 2
+    while p + 4 <= len(jpg) and jpg[p] == 0xFF:
+        m, ln = jpg[p + 1], int.from_bytes(jpg[p + 2:p + 4], "big")
+        if m == 0xFF:
+            p += 1
+            continue
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC) and ln >= 7:
+            return int.from_bytes(jpg[p + 7:p + 9], "big"), int.from_bytes(jpg[p + 5:p + 7], "big")
+        if m == 0xDA:
+            break
+        p += 2 + ln
+    raise ValueError("no frame header")
+
+
+class AviMjpegReader(_CameraMjpegReader):
+    """cv2.VideoCapture-like reader of a RIFF ``AVI `` file's first ``vids``
+    stream whose ``strf`` ``biCompression`` is ``MJPG`` (any case): what capture
+    cards, UVC tools and surveillance recorders write. Width and height come from
+    ``strf``, the frame rate is ``dwRate / dwScale`` of the stream's ``strh``. The
+    samples are the ``##dc`` / ``##db`` chunks of that stream in the ``movi`` list,
+    in file order (chunks padded to even sizes, ``LIST rec `` descended, other
+    streams and ``JUNK`` skipped, ``idx1`` not needed); zero-length chunks (dropped
+    frames) are skipped and not counted. The reader does not open a file without
+    such a stream, or one continued in a second ``RIFF AVIX`` segment (OpenDML,
+    files past 1 GiB, is out of scope). Interlaced files (two fields a chunk) are
+    read as their first field only."""
+
+    def _chunks(self, start, end):
+        """(id, list type or None, payload start, payload size) of the chunks in [start, end)."""
+        fp, p = self._fp, start
+        while p + 8 <= end:
+            fp.seek(p)
+            cid, size = struct.unpack("<4sI", fp.read(8))
+            kind = None
+            if cid in (b"RIFF", b"LIST"):
+                kind = fp.read(4)
+            if p + 8 + size > end:
+                size = end - p - 8   # a cut file: what is there
+            yield cid, kind, p + 8, size
+            p += 8 + size + (size & 1)
+
+    def _parse(self, path):
+        self._fp = open(path, "rb")
+        flen = os.fstat(self._fp.fileno()).st_size
+        top = list(self._chunks(0, flen))
+        if not top or top[0][0] != b"RIFF" or top[0][1] != b"AVI ":
+            raise ValueError("not a RIFF AVI file")
+        if any(c[0] == b"RIFF" for c in top[1:]):
+            raise ValueError("a second RIFF segment (OpenDML) is not read")
+        _, _, a, n = top[0]
+        stream, movi = None, None
+        for cid, kind, q, m in self._chunks(a + 4, a + n):
+            if cid == b"LIST" and kind == b"hdrl" and stream is None:
+                index = 0
+                for c2, k2, q2, m2 in self._chunks(q + 4, q + m):
+                    if c2 != b"LIST" or k2 != b"strl":
+                        continue
+                    strh = strf = None
+                    for c3, _, q3, m3 in self._chunks(q2 + 4, q2 + m2):
+                        if c3 in (b"strh", b"strf"):
+                            self._fp.seek(q3)
+                            data = self._fp.read(m3)
+                            strh, strf = (data, strf) if c3 == b"strh" else (strh, data)
+                    if stream is None and strh and strf and len(strh) >= 28 and len(strf) >= 20 and \
+                            strh[:4] == b"vids" and strf[16:20].upper() == b"MJPG":
+                        scale, rate = struct.unpack_from("<II", strh, 20)
+                        w, h = struct.unpack_from("<ii", strf, 4)
+                        stream = (index, abs(w), abs(h), rate / scale if scale else 0.0)
+                    index += 1
+            elif cid == b"LIST" and kind == b"movi" and movi is None:
+                movi = (q + 4, q + m)
+        if stream is None or movi is None:
+            raise ValueError("no MJPG video stream")
+        index, self.W, self.H, self.fps = stream
+        ids = (b"%02ddc" % index, b"%02ddb" % index)
+        self.samples = []
+
+        def walk(lo, hi):
+            for cid, kind, q, m in self._chunks(lo, hi):
+                if cid == b"LIST" and kind == b"rec ":
+                    walk(q + 4, q + m)
+                elif cid in ids and m > 0:
+                    self.samples.append((q, m))
+
+        walk(*movi)
+
+
 def video_name(path: str) -> str:
     """<basename without extension> (fd:45, fd:177); a synthetic URI is named WxH."""
     if path.startswith("synthetic://"):
@@ -554,8 +758,10 @@ def open_source(path: str):
         clip = SyntheticClip(w, h, seed=int(q.get("seed", 0)), noisy=q.get("noisy", "0") in ("1", "true"))
         return _ArraySource(_SyntheticFrames(clip, int(q.get("frames", 100))), float(q.get("fps", 30)))
     if not path.endswith(".npy") and cv2 is None and os.path.isfile(path):
-        # a Motion-JPEG .mp4 of this package (DVC_VIDEO_SINK=mjpeg)
-        r = Mp4MjpegReader(path, int(os.environ.get("DVC_DEVICE", os.environ.get("LOCAL_RANK", 0))))
+        # a Motion-JPEG .mp4 of this package (DVC_VIDEO_SINK=mjpeg), or a camera's .avi / raw stream
+        ext = os.path.splitext(path)[1].lower()
+        cls = {".avi": AviMjpegReader, ".mjpeg": MjpegStreamReader, ".mjpg": MjpegStreamReader}.get(ext, Mp4MjpegReader)
+        r = cls(path, int(os.environ.get("DVC_DEVICE", os.environ.get("LOCAL_RANK", 0))))
         if r.isOpened():
             return r
     if not path.endswith(".npy") and cv2 is None:

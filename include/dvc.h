@@ -104,6 +104,16 @@ extern "C" {
                                      block_size + kernel_size <= 65, without
                                      DVC_FLAG_KEEP_PLANES                       */
 
+#define DVC_FLAG_JPEGD_CAMERA 0x100u /* dvc_jpegd_create only: the handle also takes
+                                     what cameras, capture cards and AVI files
+                                     emit: three components with 4:2:2 (luma 2x1)
+                                     or 4:4:4 sampling, and frames without DHT
+                                     segments (an undefined table slot means the
+                                     ISO/IEC 10918-1 Annex K table: slot 0
+                                     luminance, slot 1 chrominance). RGB-coded
+                                     streams are refused. Work buffers are sized
+                                     for three full planes a frame                */
+
 /* ---- frame formats (video I/O) ----------------------------- */
 /* What the worker's frames are. The reference's are packed BGR straight from
  * cv2.VideoCapture.read() (fd:87); a hardware decoder (VCN via rocDecode) or a
@@ -543,12 +553,24 @@ int dvc_jpeg_sync(dvc_jpeg* h);
  * three with 4:2:0 sampling; any DQT / DHT / DRI) to the bytes libjpeg's default
  * decoder gives — slow-integer IDCT, fancy chroma upsampling, integer YCbCr to
  * RGB — as specified in DESIGN.md "Motion-JPEG decoder". Output: packed BGR, or
- * one byte a pixel for a single-component stream. */
+ * one byte a pixel for a single-component stream.
+ * Two accepted sets. The default set is the one above. A handle created with
+ * DVC_FLAG_JPEGD_CAMERA takes the camera set: the default set, plus three
+ * components with luma factors 2x1 (4:2:2, horizontal) or 1x1 (4:4:4) and chroma
+ * 1x1, plus scans that name Huffman tables no DHT defined (the Annex K tables;
+ * a DHT that is present wins). Both refuse every other sampling (4:4:0, 4:1:1,
+ * chroma factors other than 1x1); the camera set also refuses RGB-coded streams
+ * (no JFIF APP0 and an Adobe APP14 with transform 0, or neither and component
+ * ids 'R' 'G' 'B'), which the default set refuses as 4:4:4. */
 typedef struct dvc_jpegd dvc_jpegd;
 
 /* A decoder for frames up to max_width x max_height (1..65535), max_batch
  * (0/1..DVC_MAX_BATCH) frames per device launch. hip_stream / flags as
- * dvc_jpeg_create (DVC_FLAG_DEVICE_PTRS, DVC_FLAG_JOIN_STREAM). device < 0: a
+ * dvc_jpeg_create (DVC_FLAG_DEVICE_PTRS, DVC_FLAG_JOIN_STREAM), and
+ * DVC_FLAG_JPEGD_CAMERA for the camera set: such a handle sizes its coefficient
+ * and plane buffers for 3 * up(W,16) * up(H,16) samples a frame (twice the
+ * default handle's) and refuses a largest frame for which that passes 2^31 - 1
+ * bytes of coefficients with DVC_E_UNSUPPORTED. device < 0: a
  * host-only handle that touches no GPU; only dvc_jpegd_set_header works on it.
  * Replaces the cv2.VideoCapture constructions at fd:39 and of:39,121-122. */
 int dvc_jpegd_create(int max_width, int max_height, int max_batch, int device, void* hip_stream, uint32_t flags,
@@ -558,9 +580,9 @@ void dvc_jpegd_destroy(dvc_jpegd* h);
 /* Host only: parse SOI .. SOS from the n host bytes at hdr (a whole sample will
  * do), build the decoding tables and quantisers for the frames that follow, and
  * report where the entropy data starts (*header_len), the frame size and
- * DVC_FMT_BGR or DVC_FMT_GRAY. A JPEG outside the accepted set (progressive,
- * 12-bit, 16-bit DQT, arithmetic coding, other sampling, several scans) gives
- * DVC_E_UNSUPPORTED; a cut or inconsistent header, or a frame larger than the
+ * DVC_FMT_BGR or DVC_FMT_GRAY. A JPEG outside the handle's accepted set
+ * (progressive, 12-bit, 16-bit DQT, arithmetic coding, other sampling, several
+ * scans; RGB-coded on a camera handle) gives DVC_E_UNSUPPORTED here, never later; a cut or inconsistent header, or a frame larger than the
  * handle's maximum, DVC_E_INVALID; either way the handle is unchanged. What
  * cap.read() finds at the head of each sample (fd:86-87, of:142-143). */
 int dvc_jpegd_set_header(dvc_jpegd* h, const uint8_t* hdr, size_t n, size_t* header_len, int* width, int* height,

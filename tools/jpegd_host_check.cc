@@ -7,7 +7,9 @@
 // given to a GPU:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -o jpegd_host_check tools/jpegd_host_check.cc
-//   jpegd_host_check IN_DIR OUT_DIR
+//   jpegd_host_check IN_DIR OUT_DIR [camera]
+// (`camera`: the wider stream set of a DVC_FLAG_JPEGD_CAMERA handle: 4:2:2, 4:4:4
+// and frames without DHT segments.)
 // Every IN_DIR/*.jpg is decoded; OUT_DIR/<name>.raw receives its pixels (packed
 // BGR, or one byte a pixel), and one line "<name> <W> <H> <channels> <status>"
 // goes to stdout: status 0, -1 damaged data / bad header, -5 unsupported stream.
@@ -45,10 +47,10 @@ std::vector<uint32_t> rst_positions(const uint8_t* d, uint32_t size)
 }
 
 // One image; the pixels into *px. Returns the status.
-int decode(const std::vector<uint8_t>& jpg, dvc::JpegdHeader* hd, std::vector<uint8_t>* px)
+int decode(const std::vector<uint8_t>& jpg, dvc::JpegdHeader* hd, std::vector<uint8_t>* px, bool camera)
 {
     const char* why = "";
-    int rc = dvc::jpegd_parse_header(jpg.data(), jpg.size(), hd, &why);
+    int rc = dvc::jpegd_parse_header(jpg.data(), jpg.size(), hd, &why, camera);
     if (rc != dvc::kJpegdOk) return rc;
     const dvc::JpegdGeom& g = hd->g;
     // the entropy data alone, in a block of exactly its size
@@ -65,7 +67,7 @@ int decode(const std::vector<uint8_t>& jpg, dvc::JpegdHeader* hd, std::vector<ui
         uint8_t* seg = new uint8_t[end - start ? end - start : 1];
         std::copy(data + start, data + end, seg);
         int16_t* sc = new int16_t[(size_t)nmcu * g.bpm * 64]();
-        rc = dvc::jpegd_segment(seg, end - start, nmcu, g.gray, &hd->t, sc);
+        rc = dvc::jpegd_segment(seg, end - start, nmcu, g.bpm, &hd->t, sc);
         std::copy(sc, sc + (size_t)nmcu * g.bpm * 64, coef + (size_t)m0 * g.bpm * 64);
         delete[] sc;
         delete[] seg;
@@ -77,30 +79,34 @@ int decode(const std::vector<uint8_t>& jpg, dvc::JpegdHeader* hd, std::vector<ui
     }
     std::vector<uint8_t> Y((size_t)g.yw * g.yh), C[2];
     for (auto& c : C) c.resize((size_t)g.cw * g.ch);
+    const int nluma = g.gray ? 1 : g.bpm - 2;
     for (int m = 0; m < g.mcus; ++m) {
         const int my = m / g.mcus_x, mx = m % g.mcus_x;
         for (int j = 0; j < g.bpm; ++j) {
             const int16_t* lv = coef + ((size_t)m * g.bpm + j) * 64;
-            if (g.gray)
-                dvc::jpegd_idct_block(lv, hd->t.q[0], &Y[(size_t)my * 8 * g.yw + mx * 8], g.yw);
-            else if (j < 4)
-                dvc::jpegd_idct_block(lv, hd->t.q[0], &Y[(size_t)(my * 16 + (j >> 1) * 8) * g.yw + mx * 16 + (j & 1) * 8],
-                                      g.yw);
+            if (j < nluma)   // luma blocks in raster order inside the MCU
+                dvc::jpegd_idct_block(
+                    lv, hd->t.q[0], &Y[(size_t)((my * g.vs + j / g.hs) * 8) * g.yw + (mx * g.hs + j % g.hs) * 8], g.yw);
             else
-                dvc::jpegd_idct_block(lv, hd->t.q[j - 3], &C[j - 4][(size_t)my * 8 * g.cw + mx * 8], g.cw);
+                dvc::jpegd_idct_block(lv, hd->t.q[j - nluma + 1], &C[j - nluma][(size_t)my * 8 * g.cw + mx * 8], g.cw);
         }
     }
     delete[] coef;
-    const int ch = g.gray ? 1 : 3, dw = (g.W + 1) / 2, dh = (g.H + 1) / 2;
+    const int ch = g.gray ? 1 : 3, dw = (g.W + g.hs - 1) / g.hs, dh = (g.H + g.vs - 1) / g.vs;
     px->assign((size_t)g.W * g.H * ch, 0);
     for (int y = 0; y < g.H; ++y)
         for (int x = 0; x < g.W; ++x) {
             uint8_t* o = px->data() + ((size_t)y * g.W + x) * ch;
             if (g.gray)
                 o[0] = Y[(size_t)y * g.yw + x];
-            else
+            else if (g.hs == 2 && g.vs == 2)
                 dvc::jpegd_bgr(Y[(size_t)y * g.yw + x], dvc::jpegd_chroma_at(C[0].data(), g.cw, dw, dh, x, y),
                                dvc::jpegd_chroma_at(C[1].data(), g.cw, dw, dh, x, y), o);
+            else if (g.hs == 2)
+                dvc::jpegd_bgr(Y[(size_t)y * g.yw + x], dvc::jpegd_chroma_at_h2v1(C[0].data(), g.cw, dw, x, y),
+                               dvc::jpegd_chroma_at_h2v1(C[1].data(), g.cw, dw, x, y), o);
+            else   // 4:4:4: the chroma samples as they are
+                dvc::jpegd_bgr(Y[(size_t)y * g.yw + x], C[0][(size_t)y * g.cw + x], C[1][(size_t)y * g.cw + x], o);
         }
     return 0;
 }
@@ -109,8 +115,9 @@ int decode(const std::vector<uint8_t>& jpg, dvc::JpegdHeader* hd, std::vector<ui
 
 int main(int argc, char** argv)
 {
-    if (argc != 3) {
-        std::fprintf(stderr, "usage: %s IN_DIR OUT_DIR\n", argv[0]);
+    const bool camera = argc == 4 && std::string(argv[3]) == "camera";
+    if (argc != 3 && !camera) {
+        std::fprintf(stderr, "usage: %s IN_DIR OUT_DIR [camera]\n", argv[0]);
         return 2;
     }
     const std::string in = argv[1], out = argv[2];
@@ -133,7 +140,7 @@ int main(int argc, char** argv)
             std::perror(n.c_str());
             return 2;
         }
-        const int rc = decode(jpg, hd, &px);
+        const int rc = decode(jpg, hd, &px, camera);
         if (rc == 0) {
             FILE* f = std::fopen((out + "/" + n + ".raw").c_str(), "wb");
             if (!f || std::fwrite(px.data(), 1, px.size(), f) != px.size()) {
