@@ -31,6 +31,8 @@ DVC_FLAG_OUT_I420 = 0x20
 DVC_FLAG_FD_UNFUSED = 0x40
 DVC_FLAG_FD_KEPT_PLANE = 0x80
 DVC_FLAG_JPEGD_CAMERA = 0x100
+DVC_FLAG_JPEG_OPT_HUFFMAN = 0x200
+JPEG_OPT_PREFIX_MAX = 434                  # DVC_JPEG_OPT_PREFIX_MAX: the longest DHT + SOS in front of a frame
 KTIME_OUT, KTIME_FRONT_FUSED = 0, 1         # dvc_fd_ktime_kernel: which kernel KTIMING timed
 KTIME_FLOW, KTIME_FLOW_SCAN, KTIME_FLOW_SCAN2 = 2, 3, 4   # dvc_of_ktime_kernel: the level-0 flow kernel
 FMT_BGR, FMT_I420, FMT_NV12 = 0, 1, 2      # DVC_FMT_* frame formats (video I/O)
@@ -209,6 +211,10 @@ EXPORTS = list(SIGNATURES)
 REGION_SIGNATURES = {
     "dvc_quality_compare_regions": (_I, (_P, _P, _Z, _Z, _P, _Z, _Z, _P, _Z, _Z, _I, _I, _I, _P)),
 }
+# What include/dvc_jpeg_opt.h declares.
+JPEG_OPT_SIGNATURES = {
+    "dvc_jpeg_opt_tables": (_I, (_P, _PU64, _P, _Z, _PZ)),
+}
 # An older build loaded for an A/B run (DVC_LIB_PATH with DVC_ALLOW_ABI_MISMATCH=1)
 # may lack these; FDWorker.ktime_kernel and OFWorker.ktime_kernel fall back.
 OPTIONAL = ("dvc_fd_ktime_kernel", "dvc_fd_graph_stats", "dvc_of_ktime_kernel")
@@ -244,7 +250,7 @@ def lib() -> ctypes.CDLL:
                               "(set DVC_ALLOW_ABI_MISMATCH=1 to load it anyway)")
         import warnings
         warnings.warn(f"{path}: ABI version mismatch accepted (DVC_ALLOW_ABI_MISMATCH=1)")
-    for name, (restype, argtypes) in {**SIGNATURES, **REGION_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **REGION_SIGNATURES, **JPEG_OPT_SIGNATURES}.items():
         if name in OPTIONAL and not hasattr(L, name):
             continue
         fn = getattr(L, name)
@@ -419,24 +425,43 @@ class JpegEncoder(Handle):
     """cv2.VideoWriter's codec end on the GPU (dvc_jpeg): host numpy frames,
     (n, H, W, 3) BGR or (n, H, W) single-channel, -> one ``bytes`` per frame, the
     frame's JFIF entropy data and EOI; ``header`` (SOI..SOS, constant per
-    encoder) in front of it makes a complete baseline JPEG image."""
+    encoder) in front of it makes a complete baseline JPEG image.
+    ``optimize=True`` (DVC_FLAG_JPEG_OPT_HUFFMAN): Huffman tables built on the
+    GPU from the symbols of every run of ``max_batch`` frames of a call;
+    ``header`` then ends with DRI, every frame's bytes begin with its run's DHT
+    and SOS segments, ``bound`` includes them, and ``header`` + frame is a
+    complete image as before. The bytes depend on ``max_batch`` and on how
+    frames are grouped into calls, the decoded pixels do not."""
 
     _destroy = "dvc_jpeg_destroy"
 
     def __init__(self, width: int, height: int, is_color: bool = True, quality: int = 75, max_batch: int = 8,
-                 device: int = 0):
+                 device: int = 0, optimize: bool = False):
         self.W, self.H, self.is_color = int(width), int(height), bool(is_color)
         self.fmt = FMT_BGR if is_color else FMT_GRAY
+        self.optimize = bool(optimize)
         self._out = None
         self._create(lib().dvc_jpeg_create, self.W, self.H, self.fmt, int(quality), max(1, int(max_batch)),
-                     int(device), None, 0)
+                     int(device), None, DVC_FLAG_JPEG_OPT_HUFFMAN if self.optimize else 0)
         h, n = self._h, ctypes.c_size_t()
         check(lib().dvc_jpeg_header(h, None, 0, ctypes.byref(n)))
         buf = (ctypes.c_uint8 * n.value)()
         check(lib().dvc_jpeg_header(h, buf, n.value, ctypes.byref(n)))
         self.header = bytes(buf)
         check(lib().dvc_jpeg_bound(self.W, self.H, self.fmt, ctypes.byref(n)))
-        self.bound = int(n.value)
+        self.bound = int(n.value) + (JPEG_OPT_PREFIX_MAX if self.optimize else 0)
+
+    def tables(self, counts) -> bytes:
+        """dvc_jpeg_opt_tables: the DHT segment the encoder would write for the symbol
+        counts ``counts[4][256]`` (DC class 0, AC class 0, DC class 1, AC class 1)."""
+        import numpy as np
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        if c.shape != (4, 256):
+            raise ValueError(f"counts {c.shape}: (4, 256) expected")
+        n = ctypes.c_size_t()
+        buf = (ctypes.c_uint8 * 2048)()
+        check(lib().dvc_jpeg_opt_tables(self._h, c.ctypes.data_as(_PU64), buf, len(buf), ctypes.byref(n)))
+        return bytes(buf[:n.value])
 
     @staticmethod
     def alloc(shape):

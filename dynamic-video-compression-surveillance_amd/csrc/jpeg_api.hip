@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/dvc.h"
+#include "../../include/dvc_jpeg_opt.h"
 #include "host_common.h"
 #include "jpeg_kernels.h"
 #include "jpeg_tables.h"
@@ -72,8 +73,9 @@ void put16(std::vector<uint8_t>& v, unsigned x)
     v.push_back((uint8_t)x);
 }
 
-// SOI, APP0 JFIF, 2 x DQT, SOF0, 2 x DHT, DRI, SOS header.
-std::vector<uint8_t> make_header(const dvc::JpegGeom& g, const dvc::JpegTables& t)
+// SOI, APP0 JFIF, 2 x DQT, SOF0, 2 x DHT, DRI, SOS header; with optimised
+// tables the DHT and SOS segments are not here but in front of every frame.
+std::vector<uint8_t> make_header(const dvc::JpegGeom& g, const dvc::JpegTables& t, bool opt)
 {
     using namespace dvc_jpeg_tab;
     std::vector<uint8_t> v = {0xff, 0xd8, 0xff, 0xe0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
@@ -95,6 +97,7 @@ std::vector<uint8_t> make_header(const dvc::JpegGeom& g, const dvc::JpegTables& 
         int n;
     } dht[2] = {{0x00, kDcBits, kDcVals, 12}, {0x10, kAcBits, kAcVals, 162}};
     for (const auto& d : dht) {
+        if (opt) break;
         v.insert(v.end(), {0xff, 0xc4});
         put16(v, 2 + 1 + 16 + d.n);
         v.push_back(d.id);
@@ -103,6 +106,7 @@ std::vector<uint8_t> make_header(const dvc::JpegGeom& g, const dvc::JpegTables& 
     }
     v.insert(v.end(), {0xff, 0xdd, 0, 4});
     put16(v, g.mcus_x);
+    if (opt) return v;
     v.insert(v.end(), {0xff, 0xda});
     put16(v, 6 + 2 * nc);
     v.push_back((uint8_t)nc);
@@ -152,16 +156,18 @@ int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, 
     if (quality < 1 || quality > 100) return fail(DVC_E_INVALID, "quality %d outside 1..100", quality);
     if (max_batch < 0 || max_batch > DVC_MAX_BATCH) return fail(DVC_E_INVALID, "max_batch %d outside 1..%d", max_batch,
                                                                 DVC_MAX_BATCH);
-    if (frame_bound(g) > 0x7fffffffull) return fail(DVC_E_UNSUPPORTED, "frame %dx%d too large", width, height);
+    const bool opt = flags & DVC_FLAG_JPEG_OPT_HUFFMAN;
+    const uint64_t bound = frame_bound(g) + (opt ? DVC_JPEG_OPT_PREFIX_MAX : 0);   // what a frame's slot may need
+    if (bound > 0x7fffffffull) return fail(DVC_E_UNSUPPORTED, "frame %dx%d too large", width, height);
     dvc_jpeg* h = new dvc_jpeg();
     h->g = g;
     h->device = device;
     h->max_batch = max_batch ? max_batch : 1;
     h->flags = flags;
     h->chan = g.gray ? 1 : 3;
-    h->bound = frame_bound(g);
+    h->bound = bound;
     fill_tables(quality, &h->tab);
-    h->header = make_header(g, h->tab);
+    h->header = make_header(g, h->tab, opt);
     *out = h;
     if (device < 0) return DVC_OK;   // host-only handle: dvc_jpeg_header alone
     *out = nullptr;
@@ -179,6 +185,11 @@ int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, 
     if (e == hipSuccess) e = mem.alloc(&h->b.scratch, mb * nseg * (size_t)g.segcap);
     if (e == hipSuccess) e = mem.alloc(&h->b.overflow, sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(h->b.overflow, 0, sizeof(uint32_t));
+    if (e == hipSuccess && opt) {
+        e = mem.alloc(&h->b.counts, dvc::kHuffTables * 256 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = mem.alloc(&h->b.opt, sizeof(dvc::JpegOptTables));
+        if (e == hipSuccess) e = hipMemset(h->b.opt, 0, sizeof(dvc::JpegOptTables));
+    }
     if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
         e = mem.alloc(&h->d_in, mb * h->ip * g.H);   // staged frames
         if (e == hipSuccess) e = mem.alloc(&h->d_out, mb * (size_t)h->bound);
@@ -230,6 +241,10 @@ int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t fra
             kfs = h->ip * H;
         }
         HIP_OK(dvc::jpeg_launch_dct(kd, kp, kfs, m, g, h->d_tab, h->b, st));
+        if (h->b.opt) {   // this run of frames is one table group
+            HIP_OK(dvc::jpeg_launch_hist(m, g, h->b, st));
+            HIP_OK(dvc::jpeg_launch_huff_build(g, h->b, st));
+        }
         HIP_OK(dvc::jpeg_launch_bits(m, g, h->d_tab, h->b, st));
         HIP_OK(dvc::jpeg_launch_pack(m, g, h->d_tab, h->b, st));
         if (devp) {
@@ -253,7 +268,7 @@ int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t fra
         }
         HIP_OK(hipStreamSynchronize(st));
     }
-    if (overflow) return fail(DVC_E_NOMEM, "a frame's entropy data exceeds out_stride %zu (sizes hold the needed lengths)",
+    if (overflow) return fail(DVC_E_NOMEM, "a frame's data exceeds out_stride %zu (sizes hold the needed lengths)",
                               out_stride);
     return DVC_OK;
 }
@@ -272,6 +287,43 @@ int dvc_jpeg_sync(dvc_jpeg* h)
             return fail(DVC_E_NOMEM, "a frame's entropy data exceeded its output slot (sizes hold the needed lengths)");
         }
     }
+    return DVC_OK;
+}
+
+int dvc_jpeg_opt_tables(dvc_jpeg* h, const uint64_t* counts, uint8_t* dht, size_t cap, size_t* n)
+{
+    if (!h || !counts || !n) return fail(DVC_E_INVALID, "NULL argument");
+    if (h->device < 0 || !h->b.opt)
+        return fail(DVC_E_STATE, "the table builder needs a device handle created with DVC_FLAG_JPEG_OPT_HUFFMAN");
+    uint64_t total = 0;
+    for (int k = 0; k < dvc::kHuffTables; ++k)
+        for (int s = 0; s < 256; ++s) {
+            const uint64_t c = counts[256 * k + s];
+            if (!c) continue;
+            const int size = s & 15;
+            const bool ok = k & 1 ? (s == 0x00 || s == 0xF0 || (size >= 1 && size <= 10)) : s <= 11;
+            if (!ok) return fail(DVC_E_INVALID, "a count on symbol 0x%02x of table %d, which the coder cannot emit", s, k);
+            if (k >= 2 && h->g.gray) return fail(DVC_E_INVALID, "a class 1 count on a one-component handle");
+            if (c > (1ull << 62) - total) return fail(DVC_E_INVALID, "the counts sum to 2^62 or more");
+            total += c;
+        }
+    if (!total) return fail(DVC_E_INVALID, "every count is 0");
+    HIP_OK(hipSetDevice(h->device));
+    hipStream_t st = h->stream.s;
+    dvc::JpegOptTables* d = h->b.opt;
+    uint32_t len = 0;
+    std::vector<uint8_t> prefix(sizeof(d->prefix));
+    HIP_OK(hipMemcpyAsync(h->b.counts, counts, dvc::kHuffTables * 256 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(dvc::jpeg_launch_huff_build(h->g, h->b, st));
+    HIP_OK(hipMemcpyAsync(&len, &d->prefix_len, sizeof(len), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(prefix.data(), d->prefix, prefix.size(), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const size_t sos = 8 + 2 * (size_t)h->chan;   // the SOS header behind the DHT segment
+    if (len < sos + 4 || len > prefix.size()) return fail(DVC_E_HIP, "the table builder returned %u bytes", len);
+    *n = len - sos;
+    if (!dht) return DVC_OK;   // size query
+    if (cap < *n) return fail(DVC_E_NOMEM, "the DHT segment needs %zu bytes, %zu given", *n, cap);
+    std::memcpy(dht, prefix.data(), *n);
     return DVC_OK;
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jpeg_huff_core.h"
+
 namespace dvc {
 
 // The most bits one block can take: a DC code (16 + 11 magnitude bits) and 63
@@ -18,6 +20,16 @@ struct JpegTables {
     uint32_t dc[12];     // code length << 16 | code, by DC size
     uint32_t ac[256];    // the same by (run << 4 | size); 0x00 EOB, 0xF0 ZRL
     uint8_t zpos[64];    // zigzag position of natural index i
+};
+
+// A table group's tables (DVC_FLAG_JPEG_OPT_HUFFMAN), built on the device from
+// the group's symbol counts: one DC and one AC table per class (0: luma and
+// gray, 1: Cb and Cr), and the DHT + SOS bytes in front of each of its frames.
+struct JpegOptTables {
+    uint32_t dc[2][12];    // code length << 16 | code by DC size; 0: no code
+    uint32_t ac[2][256];
+    uint32_t prefix_len;
+    uint8_t prefix[(kHuffPrefixCap + 3) & ~3];
 };
 
 // One frame's geometry. A restart segment is one MCU row: `bps` blocks in scan
@@ -40,17 +52,25 @@ struct JpegBufs {
     uint32_t* seglen;    // nseg: its bytes after stuffing
     uint8_t* scratch;    // nseg * segcap
     uint32_t* overflow;  // one word: set when a frame did not fit its output slot
+    // optimised tables only (NULL otherwise):
+    unsigned long long* counts;   // [4][256]: DC class 0, AC class 0, DC class 1, AC class 1
+    JpegOptTables* opt;
 };
 
 // n frames (rows of `pitch` bytes, frames `fstride` apart; BGR or one channel)
 // -> levels.
 hipError_t jpeg_launch_dct(const uint8_t* frames, size_t pitch, size_t fstride, int n, const JpegGeom& g,
                            const JpegTables* tab, const JpegBufs& b, hipStream_t st);
+// Optimised tables: levels of the n frames of a group -> counts (zeroed first).
+hipError_t jpeg_launch_hist(int n, const JpegGeom& g, const JpegBufs& b, hipStream_t st);
+// counts -> opt (tables and prefix).
+hipError_t jpeg_launch_huff_build(const JpegGeom& g, const JpegBufs& b, hipStream_t st);
+// The three below read b.opt's tables when it is set and `tab`'s fixed ones otherwise.
 // levels -> boff, segbits.
 hipError_t jpeg_launch_bits(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st);
 // levels, boff, segbits -> scratch, seglen.
 hipError_t jpeg_launch_pack(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st);
-// scratch, seglen -> out + f * out_stride (segments, RST markers, EOI), sizes[f].
+// scratch, seglen -> out + f * out_stride ([prefix,] segments, RST markers, EOI), sizes[f].
 hipError_t jpeg_launch_gather(int n, const JpegGeom& g, const JpegBufs& b, uint8_t* out, size_t out_stride,
                               uint32_t* sizes, hipStream_t st);
 

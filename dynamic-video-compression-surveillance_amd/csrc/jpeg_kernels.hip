@@ -194,6 +194,36 @@ __global__ __launch_bounds__(256) void k_jpeg_dct(const uint8_t* __restrict__ fr
 }
 
 // ---- entropy coding: what one lane (one zigzag coefficient) emits ---------------------
+// The symbol: the DC size on lane 0, (run & 15) << 4 | size with run >> 4 ZRLs
+// in front on a lane with a non-zero level, EOB (0x00) on lane 63 behind
+// trailing zeros, nothing (-1) elsewhere. Shared by the histogram and the coders.
+struct LaneSym {
+    int sym;    // -1: nothing
+    int val;    // the value whose `size` magnitude bits follow the code
+    int size;
+    int nzrl;   // ZRL codes in front (runs of 16 zeros)
+};
+
+__device__ __forceinline__ LaneSym lane_symbol(int lv, int lane, int pred)
+{
+    LaneSym s{-1, lv, 0, 0};
+    const unsigned long long nz = __ballot(lv != 0 && lane > 0) | 1ull;   // bit 0: the DC ends no run
+    if (lane == 0) {
+        s.val = max(-2047, min(2047, lv - pred));
+        s.size = 32 - __clz(abs(s.val));
+        s.sym = s.size;
+    } else if (lv != 0) {
+        const unsigned long long below = nz & ((1ull << lane) - 1ull);
+        const int run = lane - (63 - __clzll((long long)below)) - 1;
+        s.nzrl = run >> 4;
+        s.size = 32 - __clz(abs(lv));
+        s.sym = ((run & 15) << 4) | s.size;
+    } else if (lane == 63) {   // trailing zeros: EOB
+        s.sym = 0;
+    }
+    return s;
+}
+
 struct LaneCode {
     uint32_t code;   // Huffman code followed by the magnitude bits
     int n;           // their length (<= 27)
@@ -202,33 +232,18 @@ struct LaneCode {
 
 __device__ __forceinline__ LaneCode lane_code(int lv, int lane, int pred, const uint32_t* s_dc, const uint32_t* s_ac)
 {
-    LaneCode c{0u, 0, 0};
-    const unsigned long long nz = __ballot(lv != 0 && lane > 0) | 1ull;   // bit 0: the DC ends no run
-    int val = lv, size;
-    uint32_t e;
-    if (lane == 0) {
-        val = max(-2047, min(2047, lv - pred));
-        size = 32 - __clz(abs(val));
-        e = s_dc[size];
-    } else if (lv != 0) {
-        const unsigned long long below = nz & ((1ull << lane) - 1ull);
-        const int run = lane - (63 - __clzll((long long)below)) - 1;
-        c.nzrl = run >> 4;
-        size = 32 - __clz(abs(val));
-        e = s_ac[((run & 15) << 4) | size];
-    } else if (lane == 63) {   // trailing zeros: EOB
-        e = s_ac[0];
-        c.code = e & 0xffffu;
-        c.n = (int)(e >> 16);
-        return c;
-    } else {
-        return c;
-    }
-    const uint32_t mag = (uint32_t)(val < 0 ? val - 1 : val) & ((1u << size) - 1u);
-    c.code = ((e & 0xffffu) << size) | mag;
-    c.n = (int)(e >> 16) + size;
+    const LaneSym s = lane_symbol(lv, lane, pred);
+    LaneCode c{0u, 0, s.nzrl};
+    if (s.sym < 0) return c;
+    const uint32_t e = lane == 0 ? s_dc[s.sym] : s_ac[s.sym];
+    const uint32_t mag = (uint32_t)(s.val < 0 ? s.val - 1 : s.val) & ((1u << s.size) - 1u);
+    c.code = ((e & 0xffffu) << s.size) | mag;
+    c.n = (int)(e >> 16) + s.size;
     return c;
 }
+
+// The table class of block j of a segment: 0 luma (and gray), 1 Cb and Cr.
+__device__ __forceinline__ int block_class(int j, int gray) { return !gray && j % 6 >= 4; }
 
 // The DC predictor of block j of a segment: the previous block of its component.
 __device__ __forceinline__ int dc_pred(const int16_t* seg_levels, int j, int gray)
@@ -245,23 +260,38 @@ __device__ __forceinline__ int dc_pred(const int16_t* seg_levels, int j, int gra
 
 // One workgroup per (segment, frame): a wave per block sizes its codes (a lane
 // per coefficient, the run from a ballot), then the block scans the lengths.
+// OPT: the group's tables (k_jpeg_huff_build), one pair per class, instead of
+// the handle's fixed pair.
+template <bool OPT>
 __global__ __launch_bounds__(256) void k_jpeg_bits(JpegGeom g, const JpegTables* __restrict__ tab,
+                                                   const JpegOptTables* __restrict__ opt,
                                                    const int16_t* __restrict__ levels, uint32_t* __restrict__ boff,
                                                    uint32_t* __restrict__ segbits)
 {
-    __shared__ uint32_t s_dc[12], s_ac[256], s_w[4];
+    constexpr int NC = OPT ? 2 : 1;
+    __shared__ uint32_t s_dc[NC][12], s_ac[NC][256], s_w[4];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    s_ac[t] = tab->ac[t];
-    if (t < 12) s_dc[t] = tab->dc[t];
+    if (OPT) {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            s_ac[k][t] = opt->ac[k][t];
+            if (t < 12) s_dc[k][t] = opt->dc[k][t];
+        }
+    } else {
+        s_ac[0][t] = tab->ac[t];
+        if (t < 12) s_dc[0][t] = tab->dc[t];
+    }
     __syncthreads();
     const size_t seg = (size_t)blockIdx.y * g.nseg + blockIdx.x;
     const int16_t* lv = levels + seg * g.bps * 64;
     uint32_t* bo = boff + seg * g.bps;
-    const int zrl = (int)(s_ac[0xF0] >> 16);
+    const int zrl0 = (int)(s_ac[0][0xF0] >> 16);
     for (int j = wave; j < g.bps; j += 4) {
         const int v = lv[(size_t)j * 64 + lane];
         const int pred = lane == 0 ? dc_pred(lv, j, g.gray) : 0;
-        const LaneCode c = lane_code(v, lane, pred, s_dc, s_ac);
+        const int k = OPT ? block_class(j, g.gray) : 0;
+        const int zrl = OPT ? (int)(s_ac[k][0xF0] >> 16) : zrl0;
+        const LaneCode c = lane_code(v, lane, pred, s_dc[k], s_ac[k]);
         const uint32_t inc = wave_incl_scan((uint32_t)(c.nzrl * zrl + c.n), lane);
         if (lane == 63) bo[j] = inc;
     }
@@ -298,25 +328,36 @@ __device__ __forceinline__ void put_bits(uint32_t* buf, uint32_t pos, uint32_t v
 // atomics), then the chunk's whole bytes are written out with every 0xFF
 // followed by 0x00; the partial last byte is carried into the next chunk, and
 // the segment's last byte is padded with 1-bits.
+template <bool OPT>
 __global__ __launch_bounds__(256) void k_jpeg_pack(JpegGeom g, const JpegTables* __restrict__ tab,
+                                                   const JpegOptTables* __restrict__ opt,
                                                    const int16_t* __restrict__ levels,
                                                    const uint32_t* __restrict__ boff,
                                                    const uint32_t* __restrict__ segbits, uint8_t* __restrict__ scratch,
                                                    uint32_t* __restrict__ seglen)
 {
-    __shared__ uint32_t s_dc[12], s_ac[256], s_w[4];
+    constexpr int NC = OPT ? 2 : 1;
+    __shared__ uint32_t s_dc[NC][12], s_ac[NC][256], s_w[4];
     __shared__ uint32_t s_buf[kPackDwords];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    s_ac[t] = tab->ac[t];
-    if (t < 12) s_dc[t] = tab->dc[t];
+    if (OPT) {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            s_ac[k][t] = opt->ac[k][t];
+            if (t < 12) s_dc[k][t] = opt->dc[k][t];
+        }
+    } else {
+        s_ac[0][t] = tab->ac[t];
+        if (t < 12) s_dc[0][t] = tab->dc[t];
+    }
     const size_t seg = (size_t)blockIdx.y * g.nseg + blockIdx.x;
     const int16_t* lv = levels + seg * g.bps * 64;
     const uint32_t* bo = boff + seg * g.bps;
     uint8_t* dst = scratch + seg * g.segcap;
     const uint32_t total = segbits[seg];
     __syncthreads();
-    const uint32_t zrl_code = s_ac[0xF0] & 0xffffu;
-    const int zrl = (int)(s_ac[0xF0] >> 16);
+    const uint32_t zrl_code0 = s_ac[0][0xF0] & 0xffffu;
+    const int zrl0 = (int)(s_ac[0][0xF0] >> 16);
     uint32_t carry = 0, outpos = 0;
     for (int c0 = 0; c0 < g.bps; c0 += kJpegChunk) {
         const int cnt = min(kJpegChunk, g.bps - c0);
@@ -329,7 +370,10 @@ __global__ __launch_bounds__(256) void k_jpeg_pack(JpegGeom g, const JpegTables*
         for (int j = wave; j < cnt; j += 4) {
             const int v = lv[(size_t)(c0 + j) * 64 + lane];
             const int pred = lane == 0 ? dc_pred(lv, c0 + j, g.gray) : 0;
-            const LaneCode c = lane_code(v, lane, pred, s_dc, s_ac);
+            const int k = OPT ? block_class(c0 + j, g.gray) : 0;
+            const uint32_t zrl_code = OPT ? s_ac[k][0xF0] & 0xffffu : zrl_code0;
+            const int zrl = OPT ? (int)(s_ac[k][0xF0] >> 16) : zrl0;
+            const LaneCode c = lane_code(v, lane, pred, s_dc[k], s_ac[k]);
             const uint32_t mine = (uint32_t)(c.nzrl * zrl + c.n);
             uint32_t pos = bo[c0 + j] - bit0 + wave_incl_scan(mine, lane) - mine;
             for (int z = 0; z < c.nzrl; ++z, pos += zrl) put_bits(s_buf, pos, zrl_code, zrl);
@@ -370,18 +414,187 @@ __global__ __launch_bounds__(256) void k_jpeg_pack(JpegGeom g, const JpegTables*
     if (t == 0) seglen[seg] = outpos;
 }
 
+// ---- k_jpeg_hist ------------------------------------------------------------------
+// One workgroup per (segment, frame), a wave per block, a lane per coefficient
+// (k_jpeg_bits' shape): the symbols of the segment are counted per table class
+// in LDS (a segment's counts fit 32 bits) and the non-zero counters added to the
+// group's counts[4][256] (DC class 0, AC class 0, DC class 1, AC class 1).
+// Integer sums: the result does not depend on the order of the atomics.
+__global__ __launch_bounds__(256) void k_jpeg_hist(JpegGeom g, const int16_t* __restrict__ levels,
+                                                   unsigned long long* __restrict__ counts)
+{
+    constexpr int NS = 12 + 256;
+    __shared__ uint32_t s_h[2 * NS];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    for (int i = t; i < 2 * NS; i += 256) s_h[i] = 0u;
+    __syncthreads();
+    const size_t seg = (size_t)blockIdx.y * g.nseg + blockIdx.x;
+    const int16_t* lv = levels + seg * g.bps * 64;
+    for (int j = wave; j < g.bps; j += 4) {
+        const int v = lv[(size_t)j * 64 + lane];
+        const int pred = lane == 0 ? dc_pred(lv, j, g.gray) : 0;
+        const LaneSym s = lane_symbol(v, lane, pred);
+        uint32_t* h = s_h + block_class(j, g.gray) * NS;
+        if (s.sym >= 0) atomicAdd(&h[lane == 0 ? min(s.sym, 11) : 12 + (s.sym & 255)], 1u);
+        if (s.nzrl) atomicAdd(&h[12 + 0xF0], (uint32_t)s.nzrl);
+    }
+    __syncthreads();
+    for (int i = t; i < 2 * NS; i += 256) {
+        const uint32_t c = s_h[i];
+        if (!c) continue;
+        const int cls = i >= NS, r = i - cls * NS;
+        atomicAdd(&counts[(size_t)(2 * cls + (r >= 12)) * 256 + (r >= 12 ? r - 12 : r)], (unsigned long long)c);
+    }
+}
+
+// ---- k_jpeg_huff_build ------------------------------------------------------------
+// counts[4][256] -> the group's tables and its DHT + SOS prefix; jpeg_huff_core.h
+// is the serial statement. One workgroup, a wave per table. A lane owns the
+// symbols lane + 64 k (k < 5; 256 is the reserved one): a merge of K.2 is one
+// wave-wide reduction to the two least keys (frequency, then the larger index),
+// and "every symbol of both groups one bit longer" one step on a per-symbol
+// group id. At most 256 merges; no count can make a loop run on.
+struct HuffKey {
+    unsigned long long f;   // ~0: none
+    int i;                  // -1: none
+};
+
+__device__ __forceinline__ bool huff_before(const HuffKey& a, const HuffKey& b)
+{
+    return a.f < b.f || (a.f == b.f && a.i > b.i);
+}
+
+// (a1, a2) <- the two least of {a1, a2, b1, b2}, given a1 <= a2 and b1 <= b2.
+__device__ __forceinline__ void huff_least2(HuffKey& a1, HuffKey& a2, const HuffKey& b1, const HuffKey& b2)
+{
+    if (huff_before(b1, a1)) {
+        a2 = huff_before(a1, b2) ? a1 : b2;
+        a1 = b1;
+    } else if (huff_before(b1, a2)) {
+        a2 = b1;
+    }
+}
+
+__device__ __forceinline__ HuffKey huff_shfl_xor(const HuffKey& k, int d)
+{
+    return HuffKey{__shfl_xor(k.f, d, 64), __shfl_xor(k.i, d, 64)};
+}
+
+__global__ __launch_bounds__(256) void k_jpeg_huff_build(const unsigned long long* __restrict__ counts, int nc,
+                                                         JpegOptTables* __restrict__ out)
+{
+    __shared__ uint16_t s_size[kHuffTables][kHuffSyms + 1];
+    __shared__ uint32_t s_cnt[kHuffTables][kHuffMaxDepth + 2];
+    __shared__ uint16_t s_bits[kHuffTables][kHuffMaxDepth + 2];
+    __shared__ uint8_t s_vals[kHuffTables][256];
+    __shared__ uint32_t s_code[kHuffTables][256];
+    __shared__ int s_nvals[kHuffTables];
+    __shared__ uint8_t s_prefix[(kHuffPrefixCap + 3) & ~3];
+    __shared__ int s_plen;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const unsigned long long* c = counts + 256 * w;
+    const HuffKey none{~0ull, -1};
+    unsigned long long freq[5];
+    int size[5], group[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int s = lane + 64 * k;
+        freq[k] = s < 256 ? c[s] : (s == 256 ? 1ull : 0ull);
+        size[k] = 0;
+        group[k] = s;
+        if (k < 4) s_code[w][s] = 0u;
+    }
+    for (int l = lane; l < kHuffMaxDepth + 2; l += 64) s_cnt[w][l] = 0u;
+    for (int merge = 0; merge < 256; ++merge) {
+        HuffKey m1 = none, m2 = none;
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            if (freq[k]) huff_least2(m1, m2, HuffKey{freq[k], lane + 64 * k}, none);
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const HuffKey o1 = huff_shfl_xor(m1, d), o2 = huff_shfl_xor(m2, d);
+            huff_least2(m1, m2, o1, o2);
+        }
+        if (m2.i < 0) break;   // one group left (the same in every lane)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int s = lane + 64 * k;
+            if (s == m1.i) freq[k] = m1.f + m2.f;
+            if (s == m2.i) freq[k] = 0;
+            if (group[k] == m1.i || group[k] == m2.i) {
+                ++size[k];
+                group[k] = m1.i;
+            }
+        }
+    }
+    int deepest = 0, nvals = 0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int s = lane + 64 * k;
+        if (s < kHuffSyms) s_size[w][s] = (uint16_t)size[k];
+        deepest = max(deepest, size[k]);
+        if (k < 4) nvals += __popcll(__ballot(size[k] > 0));
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) deepest = max(deepest, __shfl_xor(deepest, d, 64));
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        if (size[k] > 0) atomicAdd(&s_cnt[w][min(size[k], kHuffMaxDepth)], 1u);
+    __syncthreads();
+    for (int l = lane; l < kHuffMaxDepth + 2; l += 64) s_bits[w][l] = (uint16_t)s_cnt[w][l];
+    // HUFFVAL: a symbol's place is the number of coded symbols in front of it
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (size[k] <= 0) continue;
+        const int s = lane + 64 * k;
+        int rank = 0;
+        for (int o = 0; o < 256; ++o) {
+            const int so = s_size[w][o];
+            rank += so > 0 && (so < size[k] || (so == size[k] && o < s));
+        }
+        s_vals[w][rank] = (uint8_t)s;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        const bool any = huff_limit_bits(s_bits[w], deepest);
+        s_nvals[w] = any ? nvals : 0;
+        huff_codes(s_bits[w], s_vals[w], s_nvals[w], s_code[w]);
+    }
+    __syncthreads();
+    if (t == 0) {
+        int at = 4;
+        for (int k = 0; k < kHuffTables; ++k)
+            if (s_nvals[k]) at = huff_put_table(s_prefix, at, (k & 1) << 4 | k >> 1, s_bits[k], s_vals[k], s_nvals[k]);
+        huff_put_dht_head(s_prefix, at - 4);
+        s_plen = huff_put_sos(s_prefix, at, nc);
+    }
+    __syncthreads();
+    for (int k = 0; k < 2; ++k) {
+        out->ac[k][t] = s_code[2 * k + 1][t];
+        if (t < 12) out->dc[k][t] = s_code[2 * k][t];
+    }
+    const int plen = s_plen;
+    for (int i = t; i < plen; i += 256) out->prefix[i] = s_prefix[i];
+    if (t == 0) out->prefix_len = (uint32_t)plen;
+}
+
 // ---- k_jpeg_gather ----------------------------------------------------------------
 // One workgroup per (segment, frame): the segment's place is the sum of the
 // lengths before it plus their 2-byte RST markers; the last segment is followed
-// by EOI. A frame that does not fit its slot is not written at all.
+// by EOI. A frame that does not fit its slot is not written at all. opt (may be
+// NULL): the group's DHT + SOS prefix goes in front of every frame's first
+// segment and counts in its size.
 __global__ __launch_bounds__(256) void k_jpeg_gather(JpegGeom g, const uint8_t* __restrict__ scratch,
-                                                     const uint32_t* __restrict__ seglen, uint8_t* __restrict__ out,
+                                                     const uint32_t* __restrict__ seglen,
+                                                     const JpegOptTables* __restrict__ opt, uint8_t* __restrict__ out,
                                                      size_t out_stride, uint32_t* __restrict__ sizes,
                                                      uint32_t* __restrict__ overflow)
 {
     __shared__ uint32_t s_w[4];
     const int t = threadIdx.x, s = blockIdx.x;
     const uint32_t* sl = seglen + (size_t)blockIdx.y * g.nseg;
+    const uint32_t plen = opt ? min(opt->prefix_len, (uint32_t)kHuffPrefixCap) : 0u;
     uint32_t before = 0, all = 0;
     for (int i = t; i < g.nseg; i += 256) {
         const uint32_t n = sl[i] + 2u;   // its RST marker, or EOI after the last
@@ -391,6 +604,8 @@ __global__ __launch_bounds__(256) void k_jpeg_gather(JpegGeom g, const uint8_t* 
     uint32_t need, pre;
     (void)block_excl_scan(all, s_w, &need);
     (void)block_excl_scan(before, s_w, &pre);
+    need += plen;
+    pre += plen;
     const bool fits = (size_t)need <= out_stride;
     if (s == 0 && t == 0) {
         sizes[blockIdx.y] = need;
@@ -401,6 +616,10 @@ __global__ __launch_bounds__(256) void k_jpeg_gather(JpegGeom g, const uint8_t* 
     const uint8_t* src = scratch + ((size_t)blockIdx.y * g.nseg + s) * g.segcap;
     uint8_t* dst = out + (size_t)blockIdx.y * out_stride + pre;
     for (uint32_t i = t; i < len; i += 256) dst[i] = src[i];
+    if (s == 0) {
+        uint8_t* head = out + (size_t)blockIdx.y * out_stride;
+        for (uint32_t i = t; i < plen; i += 256) head[i] = opt->prefix[i];
+    }
     if (t == 0) {
         dst[len] = 0xff;
         dst[len + 1] = s == g.nseg - 1 ? (uint8_t)0xd9 : (uint8_t)(0xd0 + (s & 7));
@@ -421,17 +640,39 @@ hipError_t jpeg_launch_dct(const uint8_t* frames, size_t pitch, size_t fstride, 
     return hipGetLastError();
 }
 
+hipError_t jpeg_launch_hist(int n, const JpegGeom& g, const JpegBufs& b, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(b.counts, 0, kHuffTables * 256 * sizeof(unsigned long long), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_jpeg_hist, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, b.levels, b.counts);
+    return hipGetLastError();
+}
+
+hipError_t jpeg_launch_huff_build(const JpegGeom& g, const JpegBufs& b, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_jpeg_huff_build, dim3(1), dim3(256), 0, st, b.counts, g.gray ? 1 : 3, b.opt);
+    return hipGetLastError();
+}
+
 hipError_t jpeg_launch_bits(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_jpeg_bits, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, tab, b.levels, b.boff,
-                       b.segbits);
+    const dim3 grid((unsigned)g.nseg, (unsigned)n);
+    if (b.opt)
+        hipLaunchKernelGGL(k_jpeg_bits<true>, grid, dim3(256), 0, st, g, tab, b.opt, b.levels, b.boff, b.segbits);
+    else
+        hipLaunchKernelGGL(k_jpeg_bits<false>, grid, dim3(256), 0, st, g, tab, b.opt, b.levels, b.boff, b.segbits);
     return hipGetLastError();
 }
 
 hipError_t jpeg_launch_pack(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_jpeg_pack, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, tab, b.levels, b.boff,
-                       b.segbits, b.scratch, b.seglen);
+    const dim3 grid((unsigned)g.nseg, (unsigned)n);
+    if (b.opt)
+        hipLaunchKernelGGL(k_jpeg_pack<true>, grid, dim3(256), 0, st, g, tab, b.opt, b.levels, b.boff, b.segbits,
+                           b.scratch, b.seglen);
+    else
+        hipLaunchKernelGGL(k_jpeg_pack<false>, grid, dim3(256), 0, st, g, tab, b.opt, b.levels, b.boff, b.segbits,
+                           b.scratch, b.seglen);
     return hipGetLastError();
 }
 
@@ -439,7 +680,7 @@ hipError_t jpeg_launch_gather(int n, const JpegGeom& g, const JpegBufs& b, uint8
                               uint32_t* sizes, hipStream_t st)
 {
     hipLaunchKernelGGL(k_jpeg_gather, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, b.scratch, b.seglen,
-                       out, out_stride, sizes, b.overflow);
+                       b.opt, out, out_stride, sizes, b.overflow);
     return hipGetLastError();
 }
 

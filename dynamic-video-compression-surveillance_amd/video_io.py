@@ -22,7 +22,9 @@ the accelerated path. Here:
   with ``DVC_VIDEO_SINK=mjpeg`` — as a real ``.mp4``: Motion-JPEG in ISO BMFF
   (an ``mp4v`` sample entry whose ``esds`` says objectTypeIndication 0x6C,
   ISO/IEC 10918-1), every frame a baseline JPEG encoded on the GPU by
-  ``dvc_jpeg_encode`` at ``DVC_VIDEO_QUALITY`` (default 75). These are not the
+  ``dvc_jpeg_encode`` at ``DVC_VIDEO_QUALITY`` (default 75), with the fixed
+  Huffman tables or, with ``DVC_VIDEO_HUFFMAN=optimized``, tables built on the
+  GPU for every batch of frames. These are not the
   reference's MPEG-4 Part 2 files (intra-only, another codec: sizes are not
   comparable with its), but they are compressed, so the size reduction
   ``performance_analysis`` reports means something;
@@ -314,15 +316,18 @@ class Mp4MjpegWriter:
     single-channel when ``is_color`` is false) are JPEG-encoded on the GPU in
     batches of ``batch`` (the rest at release) and muxed by :class:`Mp4Muxer`.
     ``encoder``: anything with ``header`` and ``encode(frames) -> [bytes]``
-    (default: :class:`_native.JpegEncoder` on ``device``)."""
+    (default: :class:`_native.JpegEncoder` on ``device``; ``optimize=True``:
+    with Huffman tables built on the GPU for every batch)."""
 
     def __init__(self, path: str, fps: float, size, is_color: bool = True, device: int = 0, quality: int = 75,
-                 batch: int = 8, encoder=None):
+                 batch: int = 8, encoder=None, optimize: bool = False):
         self.path, self.W, self.H, self.is_color = path, int(size[0]), int(size[1]), bool(is_color)
         self.n, self._batch, self._fill = 0, max(1, int(batch)), 0
         if encoder is None:
             from ._native import JpegEncoder
-            encoder = JpegEncoder(self.W, self.H, self.is_color, quality, self._batch, device)
+            # (the keyword only when set: an encoder class put in JpegEncoder's place may know nothing of it)
+            opt = {"optimize": True} if optimize else {}
+            encoder = JpegEncoder(self.W, self.H, self.is_color, quality, self._batch, device, **opt)
         self._enc = encoder
         self._shape = (self.H, self.W, 3) if self.is_color else (self.H, self.W)
         # the pending batch; the GPU encoder hands out page-locked memory for it
@@ -838,7 +843,11 @@ def open_sink(path: str, fps: float, size, is_color: bool = True):
         return Y4mWriter(root + ".y4m", fps, size, is_color, dev)
     if ext != ".npy" and cv2 is None and os.environ.get("DVC_VIDEO_SINK", "npy") == "mjpeg":
         dev = int(os.environ.get("DVC_DEVICE", os.environ.get("LOCAL_RANK", 0)))
-        return Mp4MjpegWriter(path, fps, size, is_color, dev, int(os.environ.get("DVC_VIDEO_QUALITY", 75)))
+        huffman = os.environ.get("DVC_VIDEO_HUFFMAN", "fixed")
+        if huffman not in ("fixed", "optimized"):
+            raise ValueError(f"DVC_VIDEO_HUFFMAN={huffman!r}: fixed or optimized")
+        return Mp4MjpegWriter(path, fps, size, is_color, dev, int(os.environ.get("DVC_VIDEO_QUALITY", 75)),
+                              optimize=huffman == "optimized")
     if cv2 is not None and ext != ".npy":
         fourcc = cv2.VideoWriter_fourcc(*"mp4v")
         return cv2.VideoWriter(path, fourcc, fps, tuple(size), isColor=is_color)

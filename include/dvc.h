@@ -114,6 +114,21 @@ extern "C" {
                                      streams are refused. Work buffers are sized
                                      for three full planes a frame                */
 
+#define DVC_FLAG_JPEG_OPT_HUFFMAN 0x200u /* the Motion-JPEG encoder's create only:
+                                     Huffman tables built on the GPU from the
+                                     symbol counts of every table group (the
+                                     frames of one device launch: a call's
+                                     frames in runs of max_batch), one DC and
+                                     one AC table for luma, one pair for Cb and
+                                     Cr, instead of the fixed pair. The header
+                                     then ends with DRI, and every frame starts
+                                     with its group's DHT segment and the SOS
+                                     header (DESIGN.md "Optimised Huffman
+                                     tables")                                    */
+/* The longest DHT + SOS such a frame starts with: a DHT segment of four tables
+ * (2 + 2 + 2 * (17 + 12) + 2 * (17 + 162) = 420 bytes) and a 14-byte SOS. */
+#define DVC_JPEG_OPT_PREFIX_MAX 434
+
 /* ---- frame formats (video I/O) ----------------------------- */
 /* What the worker's frames are. The reference's are packed BGR straight from
  * cv2.VideoCapture.read() (fd:87); a hardware decoder (VCN via rocDecode) or a
@@ -512,26 +527,37 @@ void dvc_ofc_destroy(dvc_ofc* h);
  * data and EOI (dvc_jpeg_encode). The files are Motion-JPEG, not MPEG-4 Part 2.
  * The arithmetic is integer throughout and specified in DESIGN.md "Motion-JPEG
  * stream": JFIF full-range YCbCr, 4:2:0 (DVC_FMT_BGR) or one component
- * (DVC_FMT_GRAY), an exact integer DCT, IJG quality scaling, the project's fixed
- * Huffman tables (csrc/jpeg_tables.h), one restart interval per MCU row. */
+ * (DVC_FMT_GRAY), an exact integer DCT, IJG quality scaling, one restart interval
+ * per MCU row, and either the project's fixed Huffman tables (csrc/jpeg_tables.h,
+ * one DC and one AC table for every component) or, with
+ * DVC_FLAG_JPEG_OPT_HUFFMAN, tables built on the GPU from each table group's own
+ * symbol counts. The decoded pixels are the same in both modes. */
 typedef struct dvc_jpeg dvc_jpeg;
 
 /* An encoder for width x height frames (1..65520) of DVC_FMT_BGR or DVC_FMT_GRAY,
  * quality 1..100, max_batch (0/1..DVC_MAX_BATCH) frames per device launch.
- * hip_stream / flags as dvc_ofc_create (DVC_FLAG_DEVICE_PTRS, DVC_FLAG_JOIN_STREAM).
- * device < 0: a host-only handle that touches no GPU; only dvc_jpeg_header works
- * on it. Replaces the VideoWriter constructions at fd:63-65 and of:50-52,135-136. */
+ * hip_stream / flags as dvc_ofc_create (DVC_FLAG_DEVICE_PTRS, DVC_FLAG_JOIN_STREAM),
+ * and DVC_FLAG_JPEG_OPT_HUFFMAN for optimised Huffman tables: a table group is a
+ * run of max_batch frames of one dvc_jpeg_encode call, so with that flag the bytes
+ * depend on max_batch and on how frames are grouped into calls; the decoded pixels
+ * never do. device < 0: a host-only handle that touches no GPU; only
+ * dvc_jpeg_header works on it (with or without the flag). Replaces the VideoWriter
+ * constructions at fd:63-65 and of:50-52,135-136. */
 int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, int device, void* hip_stream,
                     uint32_t flags, dvc_jpeg** out);
 void dvc_jpeg_destroy(dvc_jpeg* h);
 
 /* SOI, APP0 (JFIF), two DQT, SOF0, two DHT, DRI and the SOS header: the bytes in
  * front of every frame's entropy data, constant per handle. Host only. *n
- * receives the length; dst may be NULL to query it. */
+ * receives the length; dst may be NULL to query it. With
+ * DVC_FLAG_JPEG_OPT_HUFFMAN: the same without the DHT segments and without SOS
+ * (SOI, APP0, two DQT, SOF0, DRI); the frame's own bytes begin with them, so
+ * header + frame is a complete baseline JFIF image in both modes. */
 int dvc_jpeg_header(const dvc_jpeg* h, uint8_t* dst, size_t cap, size_t* n);
 
 /* The worst-case bytes dvc_jpeg_encode writes for one frame (entropy data with
- * every byte stuffed, RST markers, EOI): an out_stride that always fits. Host only. */
+ * every byte stuffed, RST markers, EOI): an out_stride that always fits. Host only.
+ * For a handle with DVC_FLAG_JPEG_OPT_HUFFMAN add DVC_JPEG_OPT_PREFIX_MAX. */
 int dvc_jpeg_bound(int width, int height, int fmt, size_t* bytes);
 
 /* Encode n frames (frame t at frames + t*frame_stride, rows of `pitch` >= 3*W or
@@ -542,7 +568,13 @@ int dvc_jpeg_bound(int width, int height, int fmt, size_t* bytes);
  * call is asynchronous on the handle's stream (the caller's when one was joined).
  * A frame that needs more than out_stride bytes is not written (nothing is
  * written past a slot), sizes[t] still holds the needed length, and the call
- * returns DVC_E_NOMEM — with device pointers the next dvc_jpeg_sync does. */
+ * returns DVC_E_NOMEM — with device pointers the next dvc_jpeg_sync does.
+ * With DVC_FLAG_JPEG_OPT_HUFFMAN frame t's bytes are: one DHT segment with its
+ * group's tables (00, 10, 01, 11; a one-component handle: 00, 10), the SOS
+ * header (tables 00 for component 1, 11 for components 2 and 3), the entropy
+ * data and EOI; sizes[t] counts all of them and the rule for a frame that does
+ * not fit is the same. The tables are built on the device: no host
+ * synchronisation is added, and with device pointers the call stays asynchronous. */
 int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t frame_stride, int n, uint8_t* out,
                     size_t out_stride, uint32_t* sizes);
 int dvc_jpeg_sync(dvc_jpeg* h);
