@@ -64,6 +64,25 @@ def device_buf(x, tail: tuple, device: int, name: str, n: int | None = None, bat
     return int(x.data_ptr()), 1
 
 
+def device_words(x, count: int, device: int, name: str, dtype: str = "int64") -> int:
+    """Address of a device buffer of at least ``count`` words: a contiguous torch
+    CUDA tensor of ``dtype`` on the handle's device (or an explicit (address, n))."""
+    if isinstance(x, DevicePtr):
+        return x.addr
+    if isinstance(x, tuple) and len(x) == 2 and all(isinstance(v, int) for v in x):
+        return int(x[0])
+    if not _is_tensor(x):
+        raise TypeError(f"{name}: device mode needs a torch CUDA tensor, got {type(x).__name__}")
+    import torch
+    if not x.is_cuda or x.device.index != int(device):
+        raise ValueError(f"{name}: tensor is on {x.device}, the handle on cuda:{device}")
+    if x.dtype != getattr(torch, dtype):
+        raise ValueError(f"{name}: dtype {x.dtype}, expected torch.{dtype}")
+    if not x.is_contiguous() or x.numel() < count:
+        raise ValueError(f"{name}: a contiguous tensor of at least {count} words is needed, got {tuple(x.shape)}")
+    return int(x.data_ptr())
+
+
 def host_in(x, shape: tuple, name: str) -> np.ndarray:
     """A C-contiguous uint8 host array of exactly ``shape`` (copied if needed)."""
     if not isinstance(x, np.ndarray) or x.dtype != np.uint8 or x.shape != tuple(shape):

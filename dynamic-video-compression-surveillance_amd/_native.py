@@ -215,6 +215,15 @@ REGION_SIGNATURES = {
 JPEG_OPT_SIGNATURES = {
     "dvc_jpeg_opt_tables": (_I, (_P, _PU64, _P, _Z, _PZ)),
 }
+# What include/dvc_jpeg_stream.h declares.
+JPEG_STREAM_SIGNATURES = {
+    "dvc_jpeg_encode_stream": (_I, (_P, _P, _Z, _Z, _I, _P, _Z, _P)),
+}
+# What include/dvc_stream.h declares.
+STREAM_SIGNATURES = {
+    "dvc_stream_create": (_I, (_I, _PP)),
+    "dvc_stream_destroy": (_I, (_I, _P)),
+}
 # An older build loaded for an A/B run (DVC_LIB_PATH with DVC_ALLOW_ABI_MISMATCH=1)
 # may lack these; FDWorker.ktime_kernel and OFWorker.ktime_kernel fall back.
 OPTIONAL = ("dvc_fd_ktime_kernel", "dvc_fd_graph_stats", "dvc_of_ktime_kernel")
@@ -250,8 +259,10 @@ def lib() -> ctypes.CDLL:
                               "(set DVC_ALLOW_ABI_MISMATCH=1 to load it anyway)")
         import warnings
         warnings.warn(f"{path}: ABI version mismatch accepted (DVC_ALLOW_ABI_MISMATCH=1)")
-    for name, (restype, argtypes) in {**SIGNATURES, **REGION_SIGNATURES, **JPEG_OPT_SIGNATURES}.items():
-        if name in OPTIONAL and not hasattr(L, name):
+    for name, (restype, argtypes) in {**SIGNATURES, **REGION_SIGNATURES, **JPEG_OPT_SIGNATURES,
+                                      **JPEG_STREAM_SIGNATURES, **STREAM_SIGNATURES}.items():
+        # (such a build also lacks the stream output: encode_stream raises, the drivers keep the host path)
+        if (name in OPTIONAL or name in JPEG_STREAM_SIGNATURES or name in STREAM_SIGNATURES) and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -436,13 +447,19 @@ class JpegEncoder(Handle):
     _destroy = "dvc_jpeg_destroy"
 
     def __init__(self, width: int, height: int, is_color: bool = True, quality: int = 75, max_batch: int = 8,
-                 device: int = 0, optimize: bool = False):
+                 device: int = 0, optimize: bool = False, device_ptrs: bool = False, stream=None):
+        """``device_ptrs`` (DVC_FLAG_DEVICE_PTRS): :meth:`encode_stream` takes torch
+        CUDA tensors and is asynchronous on the handle's stream; ``stream``: the
+        caller's HIP stream (``torch.cuda.Stream.cuda_stream``), joined."""
         self.W, self.H, self.is_color = int(width), int(height), bool(is_color)
         self.fmt = FMT_BGR if is_color else FMT_GRAY
         self.optimize = bool(optimize)
+        self.device, self.device_ptrs, self.max_batch = int(device), bool(device_ptrs), max(1, int(max_batch))
         self._out = None
-        self._create(lib().dvc_jpeg_create, self.W, self.H, self.fmt, int(quality), max(1, int(max_batch)),
-                     int(device), None, DVC_FLAG_JPEG_OPT_HUFFMAN if self.optimize else 0)
+        flags = (DVC_FLAG_JPEG_OPT_HUFFMAN if self.optimize else 0) | (DVC_FLAG_DEVICE_PTRS if device_ptrs else 0) \
+            | (DVC_FLAG_JOIN_STREAM if stream is not None else 0)
+        self._create(lib().dvc_jpeg_create, self.W, self.H, self.fmt, int(quality), self.max_batch,
+                     self.device, ctypes.c_void_p(int(stream)) if stream is not None else None, flags)
         h, n = self._h, ctypes.c_size_t()
         check(lib().dvc_jpeg_header(h, None, 0, ctypes.byref(n)))
         buf = (ctypes.c_uint8 * n.value)()
@@ -470,6 +487,8 @@ class JpegEncoder(Handle):
 
     def encode(self, frames) -> list:
         import numpy as np
+        if self.device_ptrs:
+            raise ValueError("encode takes host frames: a device_ptrs handle has encode_stream")
         f = np.ascontiguousarray(frames, dtype=np.uint8)
         shape = (self.H, self.W, 3) if self.is_color else (self.H, self.W)
         if f.shape == shape:
@@ -493,6 +512,51 @@ class JpegEncoder(Handle):
                 break
         return [out[i, :int(sizes[i])].tobytes() for i in range(n)]
 
+    def encode_stream(self, frames, out, offsets, pitch: int = 0) -> int:
+        """dvc_jpeg_encode_stream: ``n`` frames -> complete samples (``header`` + what
+        :meth:`encode` returns) back to back in ``out``, sample t at
+        ``out[offsets[t]:offsets[t + 1]]``; returns ``n``. ``frames``: (n, H, W, 3) or
+        (n, H, W) uint8, or with ``pitch`` rows of that many bytes, (n, H, pitch).
+        ``out``: flat uint8, its length is ``cap``; ``offsets``: n + 1 words. On a
+        ``device_ptrs`` handle they are torch CUDA tensors (``offsets`` int64) and the
+        call is asynchronous: samples that do not fit ``out`` are not written and
+        :meth:`sync` raises DVC_E_NOMEM. On a host handle they are numpy arrays
+        (``offsets`` uint64) and the call itself raises it; ``offsets`` is complete
+        either way."""
+        import numpy as np
+        from . import _buffers as B
+        if not hasattr(lib(), "dvc_jpeg_encode_stream"):
+            raise DvcError(DVC_E_UNSUPPORTED, "the loaded library has no dvc_jpeg_encode_stream")
+        row = (3 if self.is_color else 1) * self.W
+        tail = (self.H, int(pitch)) if pitch else ((self.H, self.W, 3) if self.is_color else (self.H, self.W))
+        if pitch and pitch < row:
+            raise ValueError(f"pitch {pitch} below a row's {row} bytes")
+        if self.device_ptrs:
+            fa, n = B.device_buf(frames, tail, self.device, "frames")
+            oa = B.device_buf(out, tuple(out.shape[-1:]) if hasattr(out, "shape") else (), self.device, "out",
+                              batched=False)[0]
+            cap = int(out.numel()) if hasattr(out, "numel") else int(out[1])
+            pa = B.device_words(offsets, n + 1, self.device, "offsets")
+        else:
+            if self._h is None or not isinstance(frames, np.ndarray) or frames.dtype != np.uint8 \
+                    or frames.shape[1:] != tail or not frames.flags.c_contiguous:
+                raise ValueError(f"frames: expected a C-contiguous uint8 numpy array of shape (n,) + {tail}")
+            n = int(frames.shape[0])
+            if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 1 \
+                    or not out.flags.c_contiguous or not out.flags.writeable:
+                raise ValueError("out: expected a writeable flat uint8 numpy array")
+            if not isinstance(offsets, np.ndarray) or offsets.dtype != np.uint64 or offsets.ndim != 1 \
+                    or offsets.size < n + 1 or not offsets.flags.c_contiguous or not offsets.flags.writeable:
+                raise ValueError(f"offsets: expected a writeable uint64 numpy array of at least {n + 1} words")
+            fa, oa, cap, pa = frames.ctypes.data, out.ctypes.data, int(out.size), offsets.ctypes.data
+        rowp = int(pitch) if pitch else row
+        check(lib().dvc_jpeg_encode_stream(self._h, fa, rowp, rowp * self.H, n, oa, cap, pa))
+        return n
+
+    def sync(self) -> None:
+        """Wait for the handle's stream; raises what an asynchronous call could not (DVC_E_NOMEM)."""
+        check(lib().dvc_jpeg_sync(self._h))
+
 
 class JpegDecoder(Handle):
     """cv2.VideoCapture's codec end on the GPU (dvc_jpegd): whole JPEG samples
@@ -506,12 +570,53 @@ class JpegDecoder(Handle):
 
     _destroy = "dvc_jpegd_destroy"
 
-    def __init__(self, max_width: int, max_height: int, max_batch: int = 8, device: int = 0, camera: bool = False):
+    def __init__(self, max_width: int, max_height: int, max_batch: int = 8, device: int = 0, camera: bool = False,
+                 device_ptrs: bool = False, stream=None):
+        """``device_ptrs`` (DVC_FLAG_DEVICE_PTRS): the handle decodes with
+        :meth:`decode_device`, asynchronously on its stream; ``stream``: the caller's
+        HIP stream (``torch.cuda.Stream.cuda_stream``), joined."""
         self.max_batch = max(1, int(max_batch))
+        self.device, self.device_ptrs = int(device), bool(device_ptrs)
         self._in = self._out = None
         self._hdr, self.W, self.H, self.fmt = None, 0, 0, FMT_BGR
-        self._create(lib().dvc_jpegd_create, int(max_width), int(max_height), self.max_batch, int(device), None,
-                     DVC_FLAG_JPEGD_CAMERA if camera else 0)
+        flags = (DVC_FLAG_JPEGD_CAMERA if camera else 0) | (DVC_FLAG_DEVICE_PTRS if device_ptrs else 0) \
+            | (DVC_FLAG_JOIN_STREAM if stream is not None else 0)
+        self._create(lib().dvc_jpegd_create, int(max_width), int(max_height), self.max_batch, self.device,
+                     ctypes.c_void_p(int(stream)) if stream is not None else None, flags)
+
+    def decode_device(self, data, header_len: int, sizes, out, status, n: int) -> None:
+        """dvc_jpegd_decode with device pointers, asynchronous: ``n`` whole samples that
+        share the current header (:meth:`set_header`), sample t from the start of slot t
+        of ``data`` — a torch CUDA uint8 tensor (slots, stride), uploaded as read from
+        the file — decoded from byte ``header_len`` of its slot on. ``sizes``: CUDA
+        int32, the bytes of each sample behind its header (the caller keeps
+        ``header_len + sizes[t] <= stride``); ``out``: CUDA uint8 (>= n, H, W, 3), or
+        (>= n, H, W) for a single-component stream; ``status``: CUDA int32, 0 or a
+        negative DVC_E_* per frame (a damaged frame is not written). :meth:`sync`
+        waits."""
+        from . import _buffers as B
+        if not self.device_ptrs:
+            raise ValueError("decode_device needs a device_ptrs handle")
+        if self._hdr is None or int(header_len) != len(self._hdr):
+            raise ValueError("header_len is not the current header's length")
+        n = int(n)
+        if not 0 < n <= self.max_batch:
+            raise ValueError(f"{n} samples: 1..{self.max_batch} a call")
+        stride = int(data.shape[1]) if hasattr(data, "shape") and len(data.shape) == 2 else 0
+        if stride <= header_len:
+            raise ValueError("data: expected (slots, stride) with stride above header_len")
+        da = B.device_buf(data, (stride,), self.device, "data", n=n)[0]
+        shape = (self.H, self.W, 3) if self.fmt == FMT_BGR else (self.H, self.W)
+        oa = B.device_buf(out, shape, self.device, "out", n=n)[0]
+        sa = B.device_words(sizes, n, self.device, "sizes", "int32")
+        ta = B.device_words(status, n, self.device, "status", "int32")
+        pitch = shape[1] * (3 if self.fmt == FMT_BGR else 1)
+        check(lib().dvc_jpegd_decode(self._h, da + int(header_len), stride, sa, n, oa, pitch, pitch * self.H, ta))
+
+    def sync(self) -> None:
+        """Wait for the handle's stream. A damaged frame of an asynchronous call is
+        reported in its ``status`` word; the first such status is raised here, once."""
+        check(lib().dvc_jpegd_sync(self._h))
 
     def set_header(self, sample: bytes) -> int:
         """Parse ``sample``'s header; returns its length (where the entropy data starts)."""

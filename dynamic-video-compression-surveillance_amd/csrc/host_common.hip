@@ -211,3 +211,30 @@ hipError_t read_bit_plane(const uint64_t* src, size_t W, size_t H, size_t WW, ui
 }
 
 }  // namespace dvc_host
+
+// ---- include/dvc_stream.h: a stream several handles join, for callers without a HIP binding ----
+#include "../../include/dvc_stream.h"
+
+extern "C" {
+
+int dvc_stream_create(int device, void** stream)
+{
+    if (!stream) return dvc_host::fail(DVC_E_INVALID, "NULL argument");
+    *stream = nullptr;
+    HIP_OK(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    *stream = s;
+    return DVC_OK;
+}
+
+int dvc_stream_destroy(int device, void* stream)
+{
+    if (!stream) return DVC_OK;
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    HIP_OK(hipStreamDestroy(static_cast<hipStream_t>(stream)));
+    return DVC_OK;
+}
+
+}  // extern "C"

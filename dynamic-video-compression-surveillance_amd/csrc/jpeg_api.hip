@@ -9,6 +9,7 @@
 
 #include "../../include/dvc.h"
 #include "../../include/dvc_jpeg_opt.h"
+#include "../../include/dvc_jpeg_stream.h"
 #include "host_common.h"
 #include "jpeg_kernels.h"
 #include "jpeg_tables.h"
@@ -132,7 +133,43 @@ struct dvc_jpeg {
     uint8_t *d_in = nullptr, *d_out = nullptr;
     uint32_t* d_sizes = nullptr;
     size_t ip = 0;
+    // stream output (dvc_jpeg_encode_stream): the header on the device (uploaded by
+    // the first call), the end of the launch groups so far, and in host-pointer
+    // mode one group's samples and offsets (allocated by the first call)
+    uint8_t* d_header = nullptr;
+    bool header_up = false;
+    uint64_t* d_carry = nullptr;
+    uint8_t* d_sout = nullptr;
+    uint64_t* d_offs = nullptr;
 };
+
+namespace {
+
+// One launch group (m <= max_batch frames, one table group) up to its packed
+// segments: frames [staged ->] levels -> [tables ->] boff, segbits -> scratch, seglen.
+int pack_group(dvc_jpeg* h, const uint8_t* in, size_t pitch, size_t frame_stride, int m)
+{
+    const dvc::JpegGeom& g = h->g;
+    hipStream_t st = h->stream.s;
+    const uint8_t* kd = in;
+    size_t kp = pitch, kfs = frame_stride;
+    if (!(h->flags & DVC_FLAG_DEVICE_PTRS)) {   // frames up, rows of ip bytes
+        HIP_OK(dvc_host::stage_rows_h2d(h->d_in, h->ip, in, pitch, frame_stride, (size_t)h->chan * g.W, g.H, m, st));
+        kd = h->d_in;
+        kp = h->ip;
+        kfs = h->ip * g.H;
+    }
+    HIP_OK(dvc::jpeg_launch_dct(kd, kp, kfs, m, g, h->d_tab, h->b, st));
+    if (h->b.opt) {   // this run of frames is one table group
+        HIP_OK(dvc::jpeg_launch_hist(m, g, h->b, st));
+        HIP_OK(dvc::jpeg_launch_huff_build(g, h->b, st));
+    }
+    HIP_OK(dvc::jpeg_launch_bits(m, g, h->d_tab, h->b, st));
+    HIP_OK(dvc::jpeg_launch_pack(m, g, h->d_tab, h->b, st));
+    return DVC_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -185,6 +222,8 @@ int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, 
     if (e == hipSuccess) e = mem.alloc(&h->b.scratch, mb * nseg * (size_t)g.segcap);
     if (e == hipSuccess) e = mem.alloc(&h->b.overflow, sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(h->b.overflow, 0, sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(&h->d_header, h->header.size());
+    if (e == hipSuccess) e = mem.alloc(&h->d_carry, sizeof(uint64_t));
     if (e == hipSuccess && opt) {
         e = mem.alloc(&h->b.counts, dvc::kHuffTables * 256 * sizeof(unsigned long long));
         if (e == hipSuccess) e = mem.alloc(&h->b.opt, sizeof(dvc::JpegOptTables));
@@ -232,21 +271,7 @@ int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t fra
         const int m = std::min(h->max_batch, n - f0);
         const uint8_t* in = frames + (size_t)f0 * frame_stride;
         uint8_t* o = out + (size_t)f0 * out_stride;
-        const uint8_t* kd = in;
-        size_t kp = pitch, kfs = frame_stride;
-        if (!devp) {   // frames up, rows of ip bytes
-            HIP_OK(dvc_host::stage_rows_h2d(h->d_in, h->ip, in, pitch, frame_stride, roww, H, m, st));
-            kd = h->d_in;
-            kp = h->ip;
-            kfs = h->ip * H;
-        }
-        HIP_OK(dvc::jpeg_launch_dct(kd, kp, kfs, m, g, h->d_tab, h->b, st));
-        if (h->b.opt) {   // this run of frames is one table group
-            HIP_OK(dvc::jpeg_launch_hist(m, g, h->b, st));
-            HIP_OK(dvc::jpeg_launch_huff_build(g, h->b, st));
-        }
-        HIP_OK(dvc::jpeg_launch_bits(m, g, h->d_tab, h->b, st));
-        HIP_OK(dvc::jpeg_launch_pack(m, g, h->d_tab, h->b, st));
+        if (const int rc = pack_group(h, in, pitch, frame_stride, m)) return rc;
         if (devp) {
             HIP_OK(dvc::jpeg_launch_gather(m, g, h->b, o, out_stride, sizes + f0, st));
             continue;
@@ -270,6 +295,69 @@ int dvc_jpeg_encode(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t fra
     }
     if (overflow) return fail(DVC_E_NOMEM, "a frame's data exceeds out_stride %zu (sizes hold the needed lengths)",
                               out_stride);
+    return DVC_OK;
+}
+
+int dvc_jpeg_encode_stream(dvc_jpeg* h, const uint8_t* frames, size_t pitch, size_t frame_stride, int n, uint8_t* out,
+                           size_t cap, uint64_t* offsets)
+{
+    if (!h || !frames || !out || !offsets) return fail(DVC_E_INVALID, "NULL argument");
+    if (h->device < 0) return fail(DVC_E_STATE, "a host-only handle cannot encode");
+    if (n < 0) return fail(DVC_E_INVALID, "negative frame count");
+    const dvc::JpegGeom& g = h->g;
+    const size_t roww = (size_t)h->chan * g.W, H = g.H;
+    if (pitch < roww) return fail(DVC_E_INVALID, "pitch invalid");
+    if (n > 1 && frame_stride < pitch * (H - 1) + roww) return fail(DVC_E_INVALID, "frame stride invalid");
+    const bool devp = h->flags & DVC_FLAG_DEVICE_PTRS;
+    if (devp && ((uintptr_t)offsets & 7)) return fail(DVC_E_INVALID, "offsets not aligned to 8 bytes");
+    HIP_OK(hipSetDevice(h->device));
+    hipStream_t st = h->stream.s;
+    const uint32_t hl = (uint32_t)h->header.size();
+    const size_t mb = (size_t)h->max_batch;
+    if (!h->header_up) {
+        HIP_OK(hipMemcpyAsync(h->d_header, h->header.data(), hl, hipMemcpyHostToDevice, st));
+        h->header_up = true;
+    }
+    if (!devp && !h->d_sout) {   // one group's samples, each at its worst case, and its offsets
+        if (h->mem.alloc(&h->d_sout, mb * ((size_t)h->bound + hl)) != hipSuccess ||
+            h->mem.alloc(&h->d_offs, (mb + 1) * sizeof(uint64_t)) != hipSuccess) {
+            h->mem.release(h->d_sout);
+            h->d_sout = nullptr;
+            return fail(DVC_E_NOMEM, "no device memory to stage %zu samples", mb);
+        }
+    }
+    if (n == 0) {
+        if (devp) HIP_OK(hipMemsetAsync(offsets, 0, sizeof(uint64_t), st));
+        else offsets[0] = 0;
+        return DVC_OK;
+    }
+    bool overflow = false;
+    std::vector<uint64_t> ho(mb + 1);
+    for (int f0 = 0; f0 < n; f0 += h->max_batch) {
+        const int m = std::min(h->max_batch, n - f0);
+        if (const int rc = pack_group(h, frames + (size_t)f0 * frame_stride, pitch, frame_stride, m)) return rc;
+        if (devp) {   // the carry stays on the device: nothing waits between groups
+            HIP_OK(dvc::jpeg_launch_stream(m, f0 == 0, g, h->b, h->d_header, hl, h->d_carry, offsets + f0, nullptr, out,
+                                           cap, st));
+            continue;
+        }
+        HIP_OK(dvc::jpeg_launch_stream(m, f0 == 0, g, h->b, h->d_header, hl, h->d_carry, h->d_offs, h->d_offs,
+                                       h->d_sout, cap, st));
+        HIP_OK(hipMemcpyAsync(ho.data(), h->d_offs, (m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        std::memcpy(offsets + f0, ho.data(), (m + 1) * sizeof(uint64_t));
+        int fit = m;   // the samples that end inside cap come first
+        while (fit > 0 && !dvc::stream_fits(ho[fit], cap)) --fit;
+        if (fit < m) {
+            overflow = true;
+            HIP_OK(hipMemsetAsync(h->b.overflow, 0, sizeof(uint32_t), st));
+        }
+        if (ho[fit] > ho[0]) {
+            HIP_OK(hipMemcpyAsync(out + ho[0], h->d_sout, ho[fit] - ho[0], hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+        }
+    }
+    if (overflow) return fail(DVC_E_NOMEM, "the samples exceed cap %zu (offsets hold the needed places)", cap);
     return DVC_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "jpeg_huff_core.h"
+#include "jpeg_stream_core.h"
 
 namespace dvc {
 
@@ -13,6 +14,8 @@ namespace dvc {
 constexpr int kJpegMaxBlockBits = 27 + 63 * 26;
 // Blocks whose codes k_jpeg_pack assembles in LDS at a time.
 constexpr int kJpegChunk = 64;
+// The frames of one launch group of the stream output (= DVC_MAX_BATCH).
+constexpr int kJpegStreamMaxGroup = 512;
 
 // Per-handle tables in device memory.
 struct JpegTables {
@@ -73,5 +76,13 @@ hipError_t jpeg_launch_pack(int n, const JpegGeom& g, const JpegTables* tab, con
 // scratch, seglen -> out + f * out_stride ([prefix,] segments, RST markers, EOI), sizes[f].
 hipError_t jpeg_launch_gather(int n, const JpegGeom& g, const JpegBufs& b, uint8_t* out, size_t out_stride,
                               uint32_t* sizes, hipStream_t st);
+// The stream output of one launch group of n <= kJpegStreamMaxGroup frames:
+// seglen -> offsets[0..n] behind *carry (0 when `first`; left at the group's
+// end), then header, [prefix,] segments, RST markers and EOI of every sample
+// that ends inside `cap`, at out + offsets[t] - (rebase ? *rebase : 0).
+// header, carry, offsets and rebase are device pointers.
+hipError_t jpeg_launch_stream(int n, int first, const JpegGeom& g, const JpegBufs& b, const uint8_t* header,
+                              uint32_t header_len, uint64_t* carry, uint64_t* offsets, const uint64_t* rebase,
+                              uint8_t* out, uint64_t cap, hipStream_t st);
 
 }  // namespace dvc

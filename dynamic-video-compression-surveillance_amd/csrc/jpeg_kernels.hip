@@ -7,8 +7,11 @@
 //   k_jpeg_bits    per-block code lengths, bit offsets along each restart segment
 //   k_jpeg_pack    codes OR-ed into an LDS bit buffer, 0xFF stuffing -> scratch
 //   k_jpeg_gather  segments + RST markers + EOI -> the frame's output slot
+//   k_jpeg_stream_offsets, k_jpeg_stream_gather  the same segments as complete samples
+//                  back to back (dvc_jpeg_encode_stream): offsets behind a device carry,
+//                  then header, prefix, segments and markers straight to their places
 //
-// All four are integer-exact; every store is an ordinary vector store.
+// All are integer-exact; every store is an ordinary vector store.
 #include "jpeg_kernels.h"
 
 namespace dvc {
@@ -626,6 +629,73 @@ __global__ __launch_bounds__(256) void k_jpeg_gather(JpegGeom g, const uint8_t* 
     }
 }
 
+// ---- stream output (dvc_jpeg_encode_stream) ---------------------------------------
+// Complete samples back to back; the arithmetic is jpeg_stream_core.h. A frame's
+// segments sum to less than 2^31 (dvc_jpeg_create refuses larger frames), so the
+// sums inside a frame run in 32 bits and only the offsets in 64.
+
+// One workgroup per launch group of m <= DVC_MAX_BATCH frames: a wave sums a
+// frame's segments, then one thread runs the exclusive prefix behind the carry
+// of the groups before (*carry; 0 when `first`) and leaves this group's end there.
+__global__ __launch_bounds__(256) void k_jpeg_stream_offsets(JpegGeom g, const uint32_t* __restrict__ seglen,
+                                                             const JpegOptTables* __restrict__ opt,
+                                                             uint32_t header_len, int m, int first, uint64_t cap,
+                                                             uint64_t* __restrict__ carry,
+                                                             uint64_t* __restrict__ offsets,
+                                                             uint32_t* __restrict__ overflow)
+{
+    __shared__ uint64_t s_need[kJpegStreamMaxGroup];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t plen = opt ? min(opt->prefix_len, (uint32_t)kHuffPrefixCap) : 0u;
+    for (int f = wave; f < m; f += 4) {
+        uint32_t sum = (uint32_t)stream_seg_sum(seglen + (size_t)f * g.nseg, g.nseg, lane, 64);
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+        if (lane == 0) s_need[f] = stream_frame_need(header_len, plen, sum);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t ov = 0;
+        *carry = stream_group_offsets(s_need, m, first ? 0ull : *carry, cap, offsets, &ov);
+        if (ov) *overflow = 1u;
+    }
+}
+
+// One workgroup per (segment, frame), as k_jpeg_gather, but every byte goes to
+// its final place: out + offsets[f] (less *rebase, when the caller's buffer
+// begins at this group) + header + prefix + the segments before. Segment 0's
+// workgroup also writes the header and the prefix. A sample that does not lie
+// inside `cap` is not written.
+__global__ __launch_bounds__(256) void k_jpeg_stream_gather(JpegGeom g, const uint8_t* __restrict__ scratch,
+                                                            const uint32_t* __restrict__ seglen,
+                                                            const JpegOptTables* __restrict__ opt,
+                                                            const uint8_t* __restrict__ header, uint32_t header_len,
+                                                            const uint64_t* __restrict__ offsets,
+                                                            const uint64_t* __restrict__ rebase, uint64_t cap,
+                                                            uint8_t* __restrict__ out)
+{
+    __shared__ uint32_t s_w[4];
+    const int t = threadIdx.x, s = blockIdx.x, f = blockIdx.y;
+    if (!stream_fits(offsets[f + 1], cap)) return;
+    const uint32_t* sl = seglen + (size_t)f * g.nseg;
+    const uint32_t plen = opt ? min(opt->prefix_len, (uint32_t)kHuffPrefixCap) : 0u;
+    uint32_t before;
+    (void)block_excl_scan((uint32_t)stream_seg_sum(sl, s, t, 256), s_w, &before);
+    uint8_t* sample = out + (offsets[f] - (rebase ? *rebase : 0ull));
+    uint8_t* dst = sample + stream_seg_start(header_len, plen, before);
+    const uint32_t len = sl[s];
+    const uint8_t* src = scratch + ((size_t)f * g.nseg + s) * g.segcap;
+    for (uint32_t i = t; i < len; i += 256) dst[i] = src[i];
+    if (s == 0) {
+        for (uint32_t i = t; i < header_len; i += 256) sample[i] = header[i];
+        for (uint32_t i = t; i < plen; i += 256) sample[header_len + i] = opt->prefix[i];
+    }
+    if (t == 0) {
+        dst[len] = 0xff;
+        dst[len + 1] = s == g.nseg - 1 ? (uint8_t)0xd9 : (uint8_t)(0xd0 + (s & 7));
+    }
+}
+
 }  // namespace
 
 hipError_t jpeg_launch_dct(const uint8_t* frames, size_t pitch, size_t fstride, int n, const JpegGeom& g,
@@ -681,6 +751,20 @@ hipError_t jpeg_launch_gather(int n, const JpegGeom& g, const JpegBufs& b, uint8
 {
     hipLaunchKernelGGL(k_jpeg_gather, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, b.scratch, b.seglen,
                        b.opt, out, out_stride, sizes, b.overflow);
+    return hipGetLastError();
+}
+
+hipError_t jpeg_launch_stream(int n, int first, const JpegGeom& g, const JpegBufs& b, const uint8_t* header,
+                              uint32_t header_len, uint64_t* carry, uint64_t* offsets, const uint64_t* rebase,
+                              uint8_t* out, uint64_t cap, hipStream_t st)
+{
+    if (n < 1 || n > kJpegStreamMaxGroup) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_jpeg_stream_offsets, dim3(1), dim3(256), 0, st, g, b.seglen, b.opt, header_len, n, first, cap,
+                       carry, offsets, b.overflow);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_jpeg_stream_gather, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, b.scratch,
+                       b.seglen, b.opt, header, header_len, offsets, rebase, cap, out);
     return hipGetLastError();
 }
 

@@ -27,7 +27,7 @@ import os
 import time
 
 from . import video_io
-from ._dropin import ChunkPipeline
+from ._dropin import HOST_CHAIN_LINE, ChunkPipeline, chain_mode, open_chain
 from ._native import DVC_E_ODD_DCT, DvcError
 from .fd import FDWorker
 
@@ -77,6 +77,13 @@ class _Writers:
         if self.callback is not None and self.frames % 50 == 0:
             self.callback(self.frames)
 
+    def count(self, done):
+        """``done`` frames went to both sinks as encoded samples: fd:137-138 for each."""
+        for _ in range(done):
+            self.frames += 1
+            if self.callback is not None and self.frames % 50 == 0:
+                self.callback(self.frames)
+
     def release(self):
         self.mask.release()
         self.final.release()
@@ -113,36 +120,55 @@ def filter_and_dilate_movements(video_path, output_dir,
     # is: it converts on the GPU exactly as VideoCapture.read() would (fd:87)
     yuv = getattr(cap, "pixel_format", "BGR") != "BGR"
     read = cap.read_yuv if yuv else cap.read
-    ok, first = read()
+    # DVC_DEVICE_CHAIN: which ends keep their frames on the device (_dropin.DeviceChain)
+    R = max(1, READ_AHEAD)
+    blk = block_size
+    i420 = sinks.yuv and blk in (4, 8) and out_w % blk == 0 and out_h % blk == 0
+    try:
+        mode = chain_mode()
+        fshape = (src_h * 3 // 2, src_w) if yuv else (src_h, src_w, 3)
+        oshape = (out_h * 3 // 2, out_w) if i420 else (out_h, out_w, 3)
+        chain, ok, first = open_chain(mode, R, _device(), cap, [sinks.mask, sinks.final], fshape, [oshape] * 2, read)
+    except Exception:
+        cap.release()
+        sinks.release()
+        raise
     if not ok:
         logging.error("Unable to read the first frame of the video.")
         cap.release()
+        if chain is not None:
+            chain.close()
         return
 
     per_frame_s = []
     worker = None
     reader = writer = None
     try:
-        R = max(1, READ_AHEAD)
-        blk = block_size
-        i420 = sinks.yuv and blk in (4, 8) and out_w % blk == 0 and out_h % blk == 0
+        chained = chain is not None                             # an end on the device: the worker takes device frames
         worker = FDWorker(out_w, out_h, device=_device(), src_width=src_w, src_height=src_h, max_batch=R,
                           block_size=block_size, motion_threshold=motion_threshold, min_area=min_area,
                           kernel_size=kernel_size, release_factor=release_factor,
                           quantization_level=quantization_level, in_format=cap.pixel_format if yuv else "BGR",
-                          out_format="I420" if i420 else "BGR")
+                          out_format="I420" if i420 else "BGR", device_ptrs=chained,
+                          stream=chain.stream_ptr if chained else None)
         if not i420:
             sinks.yuv = False
-        worker.prime(first)                                     # fd:67-81 (resize on the GPU)
+        worker.prime(chain.on_device(first) if chained else first)   # fd:67-81 (resize on the GPU)
 
         def emit(i, ov_cp, done, failing):                      # writer thread: fd:112,131,137-138
+            if ov_cp is None:                                   # a device sink: the chain wrote the samples
+                return sinks.count(done)
             ov, cp = ov_cp
             for t in range(done):
                 sinks.emit(ov[t], cp[t])
             if failing:
                 sinks.emit(ov[done], None)
 
-        pipe = ChunkPipeline(R, worker._fshape, [worker._oshape, worker._oshape], read, emit)
+        if chained:
+            pipe, chain.emit = chain, emit
+        else:
+            pipe = ChunkPipeline(R, worker._fshape, [worker._oshape, worker._oshape], read, emit)
+        ins, outs = (pipe.d_in, pipe.d_outs) if chained else (pipe.ins, pipe.outs)
         reader, writer = pipe.start()
         handed = 0                                              # frames given to the writer
         while True:
@@ -150,10 +176,12 @@ def filter_and_dilate_movements(video_path, output_dir,
             if n == 0:
                 break
             j = pipe.out_buffer()
-            ov, cp = pipe.outs[j]
+            ov, cp = outs[j]
             stop = None
             try:                                                # fd:91-133, n times
-                worker.step_batch(pipe.ins[i][:n], ov[:n], cp[:n])
+                worker.step_batch(ins[i][:n], ov[:n], cp[:n])
+                if chained and block_size % 2:                  # asynchronous: an odd-size DCT shows at the sync
+                    worker.sync()
                 done = n
             except DvcError as e:
                 if e.code != DVC_E_ODD_DCT:
@@ -165,7 +193,7 @@ def filter_and_dilate_movements(video_path, output_dir,
                 pipe.finish()
                 raise RuntimeError("OpenCV(4.11.0) (-213:The function/feature is not implemented) "
                                    "Odd-size DCT's are not implemented in function 'apply'") from stop
-            if n < R:
+            if pipe.ended if chained else n < R:
                 break
         pipe.finish()
     except Exception as e:
@@ -175,10 +203,14 @@ def filter_and_dilate_movements(video_path, output_dir,
             pipe.stop()
             # fd:86,135 per frame: read -> last write, as the run sees it (_dropin.py)
             per_frame_s = pipe.frame_times()[:sinks.frames]
+        if mode != "off":
+            logging.info(chain.log_line() if chain is not None else HOST_CHAIN_LINE)
         cap.release()
         sinks.release()
         if worker is not None:
             worker.close()
+        if chain is not None:
+            chain.close()
 
     total_time = time.time() - t_start
     avg = sum(per_frame_s) / len(per_frame_s) if per_frame_s else 0

@@ -35,7 +35,7 @@ import os
 import time
 
 from . import _native as N
-from ._dropin import ChunkPipeline
+from ._dropin import HOST_CHAIN_LINE, ChunkPipeline, chain_mode, open_chain
 from . import video_io
 from .of import OFWorker
 
@@ -89,10 +89,23 @@ def temporal_smoothing_flow(video_path, output_dir, flow_threshold=0.5, alpha_fr
     out_overlay = video_io.open_sink(os.path.join(output_dir, save_name), fps, (width, height))
     out_mask = video_io.open_sink(os.path.join(output_dir, mask_save_name), fps, (width, height), is_color=False)
 
-    ret, first_frame = cap.read()
+    # DVC_DEVICE_CHAIN: which ends keep their frames on the device (_dropin.DeviceChain).
+    # Its outputs are the overlay (the input frames) and the mask.
+    R = max(1, READ_AHEAD)
+    try:
+        mode = chain_mode()
+        chain, ret, first_frame = open_chain(mode, R, _device(), cap, [out_overlay, out_mask], (height, width, 3),
+                                             [(height, width, 3), (height, width)], cap.read)
+    except Exception:
+        cap.release()
+        out_overlay.release()
+        out_mask.release()
+        raise
     if not ret:
         logging.error("Error: Unable to read the first frame.")
         cap.release()
+        if chain is not None:
+            chain.close()
         return 0, 0, 0
     frame_count = 0
     worker = pipe = None
@@ -101,45 +114,60 @@ def temporal_smoothing_flow(video_path, output_dir, flow_threshold=0.5, alpha_fr
         # to one step per frame): a reader thread reads ahead into page-locked
         # chunks, a writer thread writes the overlay (the frames themselves,
         # of:99) and mask videos while the next chunk runs (_dropin.py)
-        R = max(1, READ_AHEAD)
+        chained = chain is not None
         worker = OFWorker(width, height, device=_device(), flow_threshold=flow_threshold,
                           alpha_fraction=alpha_fraction, window_size=window_size, morph_kernel=morph_kernel,
-                          max_batch=R)
-        worker.prime(first_frame)
+                          max_batch=R, device_ptrs=chained, stream=chain.stream_ptr if chained else None)
+        worker.prime(chain.on_device(first_frame) if chained else first_frame)
 
         yuv = _yuv_sink(out_overlay, width, height)
 
         def emit(i, outs, done, failing):
+            if outs is None:   # a device sink: the chain wrote the samples
+                return
+            frames = outs[0] if chained else pipe.ins[i]
             if yuv and done:   # the chunk's frames as I420 in one conversion call
-                i420 = N.bgr_to_i420(pipe.ins[i][:done], out_overlay.device)
+                i420 = N.bgr_to_i420(frames[:done], out_overlay.device)
             for t in range(done):
                 if yuv:
                     out_overlay.write_yuv(i420[t])
                 else:
-                    out_overlay.write(pipe.ins[i][t])
-                out_mask.write(outs[0][t])
+                    out_overlay.write(frames[t])
+                out_mask.write(outs[-1][t])
 
-        pipe = ChunkPipeline(R, (height, width, 3), [(height, width)], cap.read, emit)
+        if chained:
+            pipe, chain.emit = chain, emit
+        else:
+            pipe = ChunkPipeline(R, (height, width, 3), [(height, width)], cap.read, emit)
         pipe.start()
         while True:
             i, n = pipe.next_chunk()
             if n == 0:
                 break
             j = pipe.out_buffer()
-            worker.step_batch(pipe.ins[i][:n], mask=pipe.outs[j][0][:n], want=("mask",))
-            pipe.write(i, j, n)
+            if chained:
+                mask = pipe.d_outs[j][1]
+                worker.step_batch(pipe.d_in[i][:n], mask=mask[:n], want=("mask",))
+                pipe.write(i, j, n, frames=[pipe.d_in[i], mask])
+            else:
+                worker.step_batch(pipe.ins[i][:n], mask=pipe.outs[j][0][:n], want=("mask",))
+                pipe.write(i, j, n)
             frame_count += n
-            if n < R:
+            if pipe.ended if chained else n < R:
                 break
         pipe.finish()
     finally:   # of:65-101 has no try: an error propagates to the caller (outputs are still released here)
         if pipe is not None:
             pipe.stop()
+        if mode != "off":
+            logging.info(chain.log_line() if chain is not None else HOST_CHAIN_LINE)
         cap.release()
         out_overlay.release()
         out_mask.release()
         if worker is not None:
             worker.close()
+        if chain is not None:
+            chain.close()
     total_time = time.time() - start_time
     avg_time = total_time / frame_count if frame_count > 0 else 0
     logging.info(f"Temporal smoothing flow completed for '{os.path.basename(video_path)}' in "

@@ -276,6 +276,15 @@ class Mp4Muxer:
         self.sizes.append(len(data))
         self._fp.write(data)
 
+    def add_samples(self, buffer, offsets) -> None:
+        """Complete JPEG images back to back (dvc_jpeg_encode_stream's layout): sample t
+        is ``buffer[offsets[t]:offsets[t + 1]]``. One ``write`` of the block."""
+        offs = [int(o) for o in offsets]
+        base = self._fp.tell() - offs[0]
+        self.offsets.extend(base + o for o in offs[:-1])
+        self.sizes.extend(b - a for a, b in zip(offs, offs[1:]))
+        self._fp.write(memoryview(buffer)[offs[0]:offs[-1]])
+
     def _moov(self) -> bytes:
         n, dur = len(self.sizes), len(self.sizes) * self.delta
         # ES_Descriptor { ES_ID 1; DecoderConfigDescriptor { objectTypeIndication 0x6C = Visual
@@ -323,6 +332,8 @@ class Mp4MjpegWriter:
                  batch: int = 8, encoder=None, optimize: bool = False):
         self.path, self.W, self.H, self.is_color = path, int(size[0]), int(size[1]), bool(is_color)
         self.n, self._batch, self._fill = 0, max(1, int(batch)), 0
+        self.device, self.quality, self.optimize, self._own_encoder = int(device), int(quality), bool(optimize), \
+            encoder is None
         if encoder is None:
             from ._native import JpegEncoder
             # (the keyword only when set: an encoder class put in JpegEncoder's place may know nothing of it)
@@ -342,6 +353,27 @@ class Mp4MjpegWriter:
             n, self._fill = self._fill, 0
             for payload in self._enc.encode(self._buf[:n]):
                 self._mux.add_sample(self._enc.header + payload)
+
+    def device_encoder(self, stream=None):
+        """A second encoder with this writer's parameters that takes device frames on
+        ``stream`` (``_native.JpegEncoder(device_ptrs=True)``) for :meth:`write_samples`;
+        ``None`` when the writer's encoder is not this package's or its library has
+        no ``dvc_jpeg_encode_stream``. Its table groups are this writer's batches."""
+        from . import _native as N
+        if not self._own_encoder or not hasattr(self._enc, "encode_stream") or \
+                not hasattr(N.lib(), "dvc_jpeg_encode_stream"):
+            return None
+        return N.JpegEncoder(self.W, self.H, self.is_color, self.quality, self._batch, self.device,
+                             optimize=self.optimize, device_ptrs=True, stream=stream)
+
+    def write_samples(self, buffer, offsets) -> None:
+        """Frames already encoded (``device_encoder().encode_stream``): complete samples
+        back to back in ``buffer``, sample t at ``offsets[t]:offsets[t + 1]``."""
+        if self._mux is None or len(offsets) < 2:
+            return
+        self._flush()
+        self._mux.add_samples(buffer, offsets)
+        self.n += len(offsets) - 1
 
     def write(self, frame: np.ndarray) -> None:
         if self._mux is None:
@@ -494,6 +526,16 @@ class Mp4MjpegReader:
         self._i += 1
         self._fp.seek(off)
         return True, self._fp.read(size)
+
+    def read_sample_into(self, dst) -> int:
+        """The next sample's bytes into ``dst`` (a writable buffer of at least its size,
+        ``samples[i][1]``) without a copy in between; the bytes read, -1 at the end."""
+        if self._fp is None or self._i >= len(self.samples):
+            return -1
+        off, size = self.samples[self._i]
+        self._i += 1
+        self._fp.seek(off)
+        return self._fp.readinto(memoryview(dst)[:size])
 
     def _pillow(self, data):
         import io
