@@ -35,6 +35,7 @@ DVC_FLAG_JPEG_OPT_HUFFMAN = 0x200
 JPEG_OPT_PREFIX_MAX = 434                  # DVC_JPEG_OPT_PREFIX_MAX: the longest DHT + SOS in front of a frame
 KTIME_OUT, KTIME_FRONT_FUSED = 0, 1         # dvc_fd_ktime_kernel: which kernel KTIMING timed
 KTIME_FLOW, KTIME_FLOW_SCAN, KTIME_FLOW_SCAN2 = 2, 3, 4   # dvc_of_ktime_kernel: the level-0 flow kernel
+ACC_FORM_GENERAL, ACC_FORM_SHORT, ACC_FORM_ROWS = 0, 1, 2   # dvc_fd_acc_form: the accumulate kernel of a handle
 FMT_BGR, FMT_I420, FMT_NV12 = 0, 1, 2      # DVC_FMT_* frame formats (video I/O)
 FMT_GRAY = 3                               # DVC_FMT_GRAY: one channel (the JPEG encoder's mask videos)
 FORMATS = {"BGR": FMT_BGR, "I420": FMT_I420, "NV12": FMT_NV12}
@@ -163,6 +164,7 @@ SIGNATURES = {
     "dvc_fd_read_plane": (_I, (_P, _I, _P)),
     "dvc_fd_ktime": (_I, (_P, _PD, _PU64, _I)),
     "dvc_fd_ktime_kernel": (_I, (_P,)),
+    "dvc_fd_acc_form": (_I, (_P,)),
     "dvc_fd_graph_stats": (_I, (_P, _PU64, _PU64)),
     "dvc_fd_destroy": (None, (_P,)),
     "dvc_contour_filter": (_I, (_P, _I, _I, ctypes.c_int64, _I, _P, _PU64)),
@@ -226,7 +228,7 @@ STREAM_SIGNATURES = {
 }
 # An older build loaded for an A/B run (DVC_LIB_PATH with DVC_ALLOW_ABI_MISMATCH=1)
 # may lack these; FDWorker.ktime_kernel and OFWorker.ktime_kernel fall back.
-OPTIONAL = ("dvc_fd_ktime_kernel", "dvc_fd_graph_stats", "dvc_of_ktime_kernel")
+OPTIONAL = ("dvc_fd_ktime_kernel", "dvc_fd_acc_form", "dvc_fd_graph_stats", "dvc_of_ktime_kernel")
 
 _lib = None
 

@@ -120,6 +120,7 @@ struct dvc_fd {
     bool resize = false;
     int fmt = DVC_FMT_BGR;  // frame format handed to prime/step (DVC_FMT_*)
     bool fused8 = false;    // DVC_FD_FUSED8=1 at create: the fused front for block_size 8 (opt-in)
+    bool acc_short = false;  // k_acc's short form: acc_fast_ok holds and DVC_ACC_GENERAL was not set at create
     int crows = 0;          // YUV: luma rows before the chroma planes (device-pointer frames)
     dvc::ResizeTab rt{};
     int B = 4, NBX = 0, NBY = 0, AP = 0;   // block size, blocks (ceil), acc pitch
@@ -350,6 +351,10 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
         // DVC_FD_GRAPH=0 (read per handle): every batch on the stage streams (tests compare both paths)
         const char* g = getenv("DVC_FD_GRAPH");
         h->graph_ok = !g || atoi(g) != 0;
+        // DVC_ACC_GENERAL=1 (read per handle): k_acc's general form even where the short
+        // form is exact (same bytes; the tests compare the two, dvc_fd_acc_form says which)
+        const char* ag = getenv("DVC_ACC_GENERAL");
+        h->acc_short = dvc::acc_fast_ok(p.alpha, p.beta, p.gamma) && !(ag && atoi(ag) != 0);
     }
     h->ofb = (p.flags & DVC_FLAG_OUT_I420) ? (size_t)p.width * p.height * 3 / 2 : (size_t)p.width * p.height * 3;
     h->crows = p.chroma_rows ? p.chroma_rows : h->sh;
@@ -1003,14 +1008,10 @@ static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fst
     a.gamma = h->p.gamma;
     a.quant = h->p.quant;
     a.qinv = 1.0 / (double)h->p.quant;
-    {
-        const float z = std::rint(std::fmaf(0.0f, h->p.alpha, std::fmaf(0.0f, h->p.beta, h->p.gamma)));
-        a.acc0_fixed = z < 0.5f && z > -0.5f;  // saturate_cast<uchar>(0) == 0 (NaN/negatives excluded)
-        const float dil1 = std::fmaf(255.0f, h->p.beta, h->p.gamma);
-        static const bool acc_general = dvc::tune_env("DVC_ACC_GENERAL") != nullptr;  // A/B: the general form always
-        a.acc_fast = dvc::acc_fast_ok(h->p.alpha, h->p.beta, h->p.gamma) && !acc_general;
-        std::memcpy(&a.dil1_bits, &dil1, 4);
-    }
+    a.acc0_fixed = dvc::acc_zero_fixed(h->p.alpha, h->p.beta, h->p.gamma);
+    a.acc_fast = h->acc_short;
+    const float dil1 = std::fmaf(255.0f, h->p.beta, h->p.gamma);
+    std::memcpy(&a.dil1_bits, &dil1, 4);
     a.M = h->M;
     a.Mtab = h->Mtab;
     a.stats = h->stats;
@@ -1305,6 +1306,13 @@ int dvc_fd_ktime_kernel(const dvc_fd* h)
 {
     if (!h) return fail(DVC_E_INVALID, "NULL handle");
     return h->last_fused ? DVC_KTIME_FRONT_FUSED : DVC_KTIME_OUT;
+}
+
+int dvc_fd_acc_form(const dvc_fd* h)
+{
+    if (!h) return fail(DVC_E_INVALID, "NULL handle");
+    if (!dvc::fast_block(h->B)) return DVC_ACC_FORM_ROWS;
+    return h->acc_short ? DVC_ACC_FORM_SHORT : DVC_ACC_FORM_GENERAL;
 }
 
 void dvc_fd_destroy(dvc_fd* h)

@@ -220,6 +220,17 @@ inline bool acc_fast_ok(float alpha, float beta, float gamma)
     return d0b == 0 && alpha >= 0.0f && alpha <= 1.0f && d1 >= 0.0f && d1 <= 255.0f &&
            __builtin_rintf(__builtin_fmaf(255.0f, alpha, d1)) <= 255.0f;
 }
+// addWeighted(acc 0, dilated 0) == 0 (BackArgs::acc0_fixed): an all-zero block
+// with no dilated pixel stays all zero. saturate_cast<uchar>(rint(.)) is 0 for
+// every value in (-0.5, 0.5), -0 included; NaN fails both comparisons.
+inline bool acc_zero_fixed(float alpha, float beta, float gamma)
+{
+    const float z = __builtin_rintf(__builtin_fmaf(0.0f, alpha, __builtin_fmaf(0.0f, beta, gamma)));
+    return z < 0.5f && z > -0.5f;
+}
+// Both are executed on the host over the accepted domain (any float triple) by
+// tools/acc_fast_host_check.cc: wherever acc_fast_ok holds, the short form
+// equals the clamped form on all 512 inputs and acc_zero_fixed holds.
 // k_out (overlay + compressed frames; no recurrence) and k_out_gen for the
 // generic layout / partial edge blocks (always launched: it also detects the
 // odd-size DCT stop and counts generic static blocks). fix: the fused front

@@ -1303,6 +1303,7 @@ __global__ void __launch_bounds__(64) k_acc(BackArgs a)
     const int bxc = min(bxi, NBX - 1);
     const size_t blk = (size_t)by * NBX + bxc, NB = (size_t)NBY * NBX;
     const int x0 = bxc * B, y0 = by * B;
+    const int vw = min(B, a.g.W - x0), vh = min(B, a.g.H - y0);   // the block's pixels (general form: the pad is masked)
     uint32_t acv[B][B / 4];
 #pragma unroll
     for (int i = 0; i < B; ++i) {
@@ -1397,6 +1398,11 @@ __global__ void __launch_bounds__(64) k_acc(BackArgs a)
                         const float c = __builtin_fminf(__builtin_fmaxf(__builtin_rintf(tv), 0.f), 255.f);
                         nv = __builtin_amdgcn_cvt_pk_u8_f32(c, (uint32_t)j, nv);
                     }
+                    // a partial edge block's pad is no pixel: it stays 0 even where
+                    // addWeighted(0, 0) != 0, or a block whose pixels are all zero
+                    // would not count as static (fd:120 looks at the slice only)
+                    if (i >= vh || 4 * q >= vw) nv = 0;
+                    else if (4 * q + 4 > vw) nv &= 0xffffffffu >> (8 * (4 * q + 4 - vw));
                     acv[i][q] = nv;
                     zero = zero && nv == 0;
                 }

@@ -23,7 +23,8 @@ from ._worker import Worker
 def derive_params(width: int, height: int, block_size: int = 4, motion_threshold: float = 0.5,
                   min_area: float = 500, kernel_size: int = 7, release_factor: float = 0.5,
                   quantization_level: float = 100, flags: int = 0, src_width: int = 0,
-                  src_height: int = 0, in_format: str = "BGR", chroma_rows: int = 0) -> N.FdParams:
+                  src_height: int = 0, in_format: str = "BGR", chroma_rows: int = 0,
+                  accumulate=None) -> N.FdParams:
     """dvc_fd_params from the reference kwargs (frame_differencing.py:21-30).
 
     * ``ithresh = floor(motion_threshold)`` clamped to [-1, 255]: cv::threshold
@@ -31,7 +32,8 @@ def derive_params(width: int, height: int, block_size: int = 4, motion_threshold
     * ``min_area2 = floor(2*min_area)``: ``contourArea > min_area`` is exactly
       ``2*area > floor(2*min_area)`` for the half-integer polygon areas (fd:103).
     * addWeighted receives (release_factor, 1 - release_factor, 0) as doubles and
-      computes in float32 (fd:107).
+      computes in float32 (fd:107). ``accumulate=(alpha, beta, gamma)`` hands
+      over raw weights instead; any float triple is accepted (include/dvc.h).
     """
     p = N.FdParams()
     p.width, p.height = int(width), int(height)
@@ -43,6 +45,8 @@ def derive_params(width: int, height: int, block_size: int = 4, motion_threshold
     p.alpha = float(release_factor)
     p.beta = float(1 - release_factor)
     p.gamma = 0.0
+    if accumulate is not None:
+        p.alpha, p.beta, p.gamma = (float(v) for v in accumulate)
     p.quant = float(quantization_level)
     p.prime_ksize = 25   # fd:77
     p.prime_sigma = 30.0
@@ -136,6 +140,14 @@ class FDWorker(Worker):
         if k < 0:
             N.check(k)
         return "k_front_fused" if k == N.KTIME_FRONT_FUSED else "k_out"
+
+    def acc_form(self) -> str:
+        """The accumulate kernel this handle launches (dvc_fd_acc_form): "short" or
+        "general" (k_acc<4 / 8>; DVC_ACC_GENERAL=1 at create forces the latter) or "rows"."""
+        k = self._lib.dvc_fd_acc_form(self._h)
+        if k < 0:
+            N.check(k)
+        return {N.ACC_FORM_GENERAL: "general", N.ACC_FORM_SHORT: "short", N.ACC_FORM_ROWS: "rows"}[k]
 
     def graph_stats(self) -> dict:
         """Batches launched as HIP graphs (the short-batch device path) and graphs built."""

@@ -185,7 +185,12 @@ int dvc_bgr_to_i420(const uint8_t* bgr, size_t bgr_pitch, size_t bgr_stride, int
  *                 k/2 (fd:80,106). 1 <= ksize <= 127 (DVC_E_UNSUPPORTED above:
  *                 a row is dilated by word shifts of at most 63 bits).
  *   alpha,beta,gamma  addWeighted weights as float32: release_factor,
- *                 1-release_factor, 0 (fd:107).
+ *                 1-release_factor, 0 (fd:107). Any float triple is accepted,
+ *                 as the reference accepts any release_factor: each pixel is
+ *                 rint(fmaf(acc, alpha, fmaf(dilated, beta, gamma))), half to
+ *                 even, saturated to [0, 255]; a NaN sum (a NaN weight,
+ *                 0 * inf, inf - inf) gives 0, as saturate_cast<uchar>(
+ *                 cvRound(NaN)) does.
  *   quant         quantization_level as float32 (fd:123).
  *   prime_ksize,prime_sigma  GaussianBlur of frame 0: 25, 30.0 (fd:77).
  *   max_batch     frames per device launch (see the field).
@@ -335,6 +340,17 @@ int dvc_fd_ktime(dvc_fd* h, double* total_ms, uint64_t* launches, int reset);
 #define DVC_KTIME_OUT 0
 #define DVC_KTIME_FRONT_FUSED 1
 int dvc_fd_ktime_kernel(const dvc_fd* h);
+
+/* Which form of the accumulate stage (fd:107) the handle launches, fixed at
+ * create: DVC_ACC_FORM_SHORT (block_size 4 / 8, weights for which the unclamped
+ * packed form is exact: 0 <= release_factor <= 1), DVC_ACC_FORM_GENERAL
+ * (block_size 4 / 8, any other weights, or DVC_ACC_GENERAL=1 in the environment
+ * at create: same bytes) or DVC_ACC_FORM_ROWS (any other block size). Negative
+ * on error. */
+#define DVC_ACC_FORM_GENERAL 0
+#define DVC_ACC_FORM_SHORT 1
+#define DVC_ACC_FORM_ROWS 2
+int dvc_fd_acc_form(const dvc_fd* h);
 
 /* Batches of device frames (DVC_FLAG_DEVICE_PTRS, frames the kernels read in
  * place, no KTIMING; not a batch of > 128 frames whose outputs overlap a batch

@@ -139,10 +139,12 @@ def _u8(a: np.ndarray):
 # ---------------------------------------------------------------- params ----
 def fd_params(width, height, block_size=4, motion_threshold=0.5, min_area=500,
               kernel_size=7, release_factor=0.5, quantization_level=100,
-              prime_ksize=25, prime_sigma=30.0, src_width=0, src_height=0) -> FdParams:
+              prime_ksize=25, prime_sigma=30.0, src_width=0, src_height=0, accumulate=None) -> FdParams:
     """Host-side derivation of dvc_fd_params from the reference kwargs
     (frame_differencing.py:21-30); same rules as the product's host code.
-    width/height are the scaled size (fd:60-61), src_* the video's (0: same)."""
+    width/height are the scaled size (fd:60-61), src_* the video's (0: same).
+    ``accumulate``: raw addWeighted weights (alpha, beta, gamma) instead of
+    (release_factor, 1 - release_factor, 0)."""
     p = FdParams()
     p.src_width, p.src_height = int(src_width), int(src_height)
     p.width, p.height, p.block = int(width), int(height), int(block_size)
@@ -153,6 +155,8 @@ def fd_params(width, height, block_size=4, motion_threshold=0.5, min_area=500,
     p.alpha = float(release_factor)
     p.beta = float(1 - release_factor)
     p.gamma = 0.0
+    if accumulate is not None:
+        p.alpha, p.beta, p.gamma = (float(v) for v in accumulate)
     p.quant = float(quantization_level)
     p.prime_ksize, p.prime_sigma = int(prime_ksize), float(prime_sigma)
     return p

@@ -273,12 +273,16 @@ void oc_dilate_rect(const uint8_t* src, int W, int H, int k, int anchor, uint8_t
 }
 
 /* addWeighted 8U, fd:107: saturate_cast<uchar>(fma(a, alpha, fma(b, beta, gamma)))
- * with float32 weights and round-half-to-even (cvRound). */
+ * with float32 weights and round-half-to-even (cvRound). Any float triple is
+ * accepted. A NaN sum (a NaN weight, 0 * inf, inf - inf) gives 0: cvRound(NaN)
+ * is INT_MIN (cvtss2si / lrint's "integer indefinite"), which
+ * saturate_cast<uchar>(int) sends to 0. The test below is written so that NaN
+ * takes its first arm and is never converted to an integer type. */
 uint8_t oc_add_weighted_px(uint8_t a, float alpha, uint8_t b, float beta, float gamma)
 {
     float t = fmaf((float)a, alpha, fmaf((float)b, beta, gamma));
     float r = rintf(t);
-    return r < 0.f ? 0 : (r > 255.f ? 255 : (uint8_t)r);
+    return !(r > 0.f) ? 0 : (r > 255.f ? 255 : (uint8_t)r);
 }
 
 /* cvtColor(BGR2YCrCb) 8U, fd:115. */

@@ -26,12 +26,12 @@ static void frame(uint8_t* f, int W, int H, int t, unsigned seed)
     }
 }
 
-static int run_fd(int sw, int sh, int W, int H, int block, int k, float r, int nf)
+static int run_fd_w(int sw, int sh, int W, int H, int block, int k, float alpha, float beta, float gamma, int nf)
 {
     dvc_fd_params p;
     memset(&p, 0, sizeof(p));
     p.width = W; p.height = H; p.block = block; p.ithresh = 0; p.min_area2 = 40; p.ksize = k; p.anchor = k / 2;
-    p.alpha = r; p.beta = 1.f - r; p.gamma = 0.f; p.quant = 100.f; p.prime_ksize = 25; p.prime_sigma = 30.0;
+    p.alpha = alpha; p.beta = beta; p.gamma = gamma; p.quant = 100.f; p.prime_ksize = 25; p.prime_sigma = 30.0;
     p.src_width = sw; p.src_height = sh;
     oc_fd* h = oc_fd_create(&p, 0);
     oc_fd* hl = oc_fd_create(&p, 1);          /* literal Suzuki path too */
@@ -54,6 +54,11 @@ static int run_fd(int sw, int sh, int W, int H, int block, int k, float r, int n
     oc_fd_destroy(h); oc_fd_destroy(hl);
     free(f); free(ov); free(cp); free(acc);
     return rc == 0 || rc == DVC_E_ODD_DCT ? 0 : 3;
+}
+
+static int run_fd(int sw, int sh, int W, int H, int block, int k, float r, int nf)
+{
+    return run_fd_w(sw, sh, W, H, block, k, r, 1.f - r, 0.f, nf);
 }
 
 static int run_of(int W, int H, int nf)
@@ -93,6 +98,17 @@ int main(void)
     rc |= run_fd(70, 50, 91, 65, 6, 3, 0.5f, 6);         /* linear upscale, b = 6 */
     rc |= run_fd(40, 36, 40, 36, 1, 5, 0.5f, 5);
     rc |= run_fd(40, 36, 40, 36, 16, 7, 0.5f, 12);
+    rc |= run_fd(64, 48, 64, 48, 4, 7, strtof("nan", NULL), 6);              /* every sum NaN: 0, no float -> byte cast */
+    rc |= run_fd(64, 48, 64, 48, 8, 7, 1.25f, 6);                            /* both clamps bind (beta = -0.25) */
+    rc |= run_fd_w(64, 48, 64, 48, 4, 7, 1.0f, 1.0f, 300.0f, 6);             /* upper clamp from gamma */
+    for (int a = 0; a < 256; ++a)                                            /* the pixel function: NaN, +-inf, far out of range */
+        for (int b = 0; b < 256; b += 255) {
+            const float inf = strtof("inf", NULL), nan = strtof("nan", NULL);
+            if (oc_add_weighted_px((uint8_t)a, nan, (uint8_t)b, 0.5f, 0.f) != 0) rc |= 8;
+            if (oc_add_weighted_px((uint8_t)a, inf, (uint8_t)b, -inf, 0.f) != 0) rc |= 8;
+            if (oc_add_weighted_px((uint8_t)a, 1.0f, (uint8_t)b, 1.0f, 3e38f) != 255) rc |= 8;
+            if (oc_add_weighted_px((uint8_t)a, 1.0f, (uint8_t)b, 1.0f, -3e38f) != 0) rc |= 8;
+        }
     rc |= run_of(96, 64, 5);
     rc |= run_of(104, 72, 4);
     printf(rc ? "FAILED\n" : "sanitized run ok\n");

@@ -38,6 +38,14 @@ CASES = {
     # cv2.dct raises on an odd side > 1 (fd:122) and the loop ends (fd:140)
     "odd_b5_stops": (lambda: clip(160, 96, 12, seed=18, n_objects=3), {"block_size": 5}),
     "odd_w163_stops": (lambda: clip(163, 96, 14, seed=19, n_objects=3), {}),
+    # the accumulated-mask recurrence (fd:107) away from release_factor 0.5 / 0.3, min_area 20 so that the
+    # moving objects are kept in every frame: no memory at all (the mask is the dilated mask); a slow
+    # build-up (+25.5 a frame towards 255); and a weight above 1, where beta is negative and, from 0, the
+    # lower clamp holds the mask at 0 for good (every block static: k_acc's general form)
+    "s160_release0": (lambda: clip(160, 96, 10, seed=23, n_objects=3), {"release_factor": 0.0, "min_area": 20}),
+    "s160_release0p9_b8": (lambda: clip(160, 96, 10, seed=24, n_objects=3),
+                           {"release_factor": 0.9, "block_size": 8, "min_area": 20}),
+    "s160_release1p25": (lambda: clip(160, 96, 10, seed=25, n_objects=3), {"release_factor": 1.25, "min_area": 20}),
 }
 # cases whose every output pixel is stored in fd_golden.npz (the rest: SHA-256 per frame)
 FULL_ARRAYS = ("s160_clean", "noise64_min100", "w162_h98_partial", "odd_w163_stops")
