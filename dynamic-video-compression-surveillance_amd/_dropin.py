@@ -178,14 +178,14 @@ def device_source(cap):
 
 def device_sinks(sinks, R):
     """(engage, reason): whether every sink is an ``Mp4MjpegWriter`` whose encoder has
-    the stream output; with optimised tables the chunks must also hold whole table
-    groups (``reason`` "groups": the host path keeps today's groups, even under on)."""
+    the stream output; with optimised tables or a rate target (both work group by
+    group) the chunks must also hold whole table groups (``reason`` "groups": the host path keeps today's groups, even under on)."""
     from . import video_io
     for s in sinks:
         if not isinstance(s, video_io.Mp4MjpegWriter) or not s._own_encoder or \
                 not hasattr(s._enc, "encode_stream") or not hasattr(N.lib(), "dvc_jpeg_encode_stream"):
             return False, "encoder"
-    if any(s.optimize and R % s._batch for s in sinks):
+    if any((s.optimize or s.target_bytes is not None) and R % s._batch for s in sinks):
         return False, "groups"
     return True, ""
 

@@ -33,6 +33,7 @@ DVC_FLAG_FD_KEPT_PLANE = 0x80
 DVC_FLAG_JPEGD_CAMERA = 0x100
 DVC_FLAG_JPEG_OPT_HUFFMAN = 0x200
 JPEG_OPT_PREFIX_MAX = 434                  # DVC_JPEG_OPT_PREFIX_MAX: the longest DHT + SOS in front of a frame
+JPEG_RATE_PREFIX_MAX = 138 + JPEG_OPT_PREFIX_MAX   # DVC_JPEG_RATE_PREFIX_MAX: DQT, DQT in front of that
 KTIME_OUT, KTIME_FRONT_FUSED = 0, 1         # dvc_fd_ktime_kernel: which kernel KTIMING timed
 KTIME_FLOW, KTIME_FLOW_SCAN, KTIME_FLOW_SCAN2 = 2, 3, 4   # dvc_of_ktime_kernel: the level-0 flow kernel
 ACC_FORM_GENERAL, ACC_FORM_SHORT, ACC_FORM_ROWS = 0, 1, 2   # dvc_fd_acc_form: the accumulate kernel of a handle
@@ -221,6 +222,13 @@ JPEG_OPT_SIGNATURES = {
 JPEG_STREAM_SIGNATURES = {
     "dvc_jpeg_encode_stream": (_I, (_P, _P, _Z, _Z, _I, _P, _Z, _P)),
 }
+# What include/dvc_jpeg_rate.h declares.
+JPEG_RATE_SIGNATURES = {
+    "dvc_jpeg_create_rate": (_I, (_I, _I, _I, _Z, _I, _I, _I, _I, _P, _U32, _PP)),
+    "dvc_jpeg_rate_stats": (_I, (_P, _P)),
+}
+JPEG_RATE_STATS = ("groups", "frames", "missed_groups", "est_bytes", "budget_bytes", "quality_frames", "q_lowest",
+                   "q_highest", "q_last")   # struct dvc_jpeg_rate_stats: uint64_t each
 # What include/dvc_stream.h declares.
 STREAM_SIGNATURES = {
     "dvc_stream_create": (_I, (_I, _PP)),
@@ -262,9 +270,11 @@ def lib() -> ctypes.CDLL:
         import warnings
         warnings.warn(f"{path}: ABI version mismatch accepted (DVC_ALLOW_ABI_MISMATCH=1)")
     for name, (restype, argtypes) in {**SIGNATURES, **REGION_SIGNATURES, **JPEG_OPT_SIGNATURES,
-                                      **JPEG_STREAM_SIGNATURES, **STREAM_SIGNATURES}.items():
-        # (such a build also lacks the stream output: encode_stream raises, the drivers keep the host path)
-        if (name in OPTIONAL or name in JPEG_STREAM_SIGNATURES or name in STREAM_SIGNATURES) and not hasattr(L, name):
+                                      **JPEG_STREAM_SIGNATURES, **JPEG_RATE_SIGNATURES, **STREAM_SIGNATURES}.items():
+        # (such a build also lacks the stream output: encode_stream raises, the drivers keep the host path;
+        # and the rate target: JpegEncoder(target_bytes=...) raises)
+        if (name in OPTIONAL or name in JPEG_STREAM_SIGNATURES or name in JPEG_RATE_SIGNATURES
+                or name in STREAM_SIGNATURES) and not hasattr(L, name):
             continue
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -444,15 +454,26 @@ class JpegEncoder(Handle):
     ``header`` then ends with DRI, every frame's bytes begin with its run's DHT
     and SOS segments, ``bound`` includes them, and ``header`` + frame is a
     complete image as before. The bytes depend on ``max_batch`` and on how
-    frames are grouped into calls, the decoded pixels do not."""
+    frames are grouped into calls, the decoded pixels do not.
+    ``target_bytes`` (dvc_jpeg_create_rate): a byte target per frame in place of
+    ``quality`` (then ignored; ``self.quality`` is None). Every run of
+    ``max_batch`` frames of a call is coded at the quality of ``quality_range``
+    that the search of DESIGN.md "Rate target" finds on the GPU; ``header`` then
+    has no DQT and no SOS, every frame's bytes begin with DQT, DQT, [DHT,] SOS,
+    and :meth:`rate_stats` tells what was chosen. The target bounds the size
+    before byte stuffing with the fixed tables, not the file's."""
 
     _destroy = "dvc_jpeg_destroy"
 
     def __init__(self, width: int, height: int, is_color: bool = True, quality: int = 75, max_batch: int = 8,
-                 device: int = 0, optimize: bool = False, device_ptrs: bool = False, stream=None):
+                 device: int = 0, optimize: bool = False, device_ptrs: bool = False, stream=None,
+                 target_bytes=None, quality_range=(10, 95)):
         """``device_ptrs`` (DVC_FLAG_DEVICE_PTRS): :meth:`encode_stream` takes torch
         CUDA tensors and is asynchronous on the handle's stream; ``stream``: the
         caller's HIP stream (``torch.cuda.Stream.cuda_stream``), joined."""
+        self.target_bytes = None if target_bytes is None else int(target_bytes)
+        self.quality_range = (int(quality_range[0]), int(quality_range[1]))
+        self.quality = int(quality) if target_bytes is None else None
         self.W, self.H, self.is_color = int(width), int(height), bool(is_color)
         self.fmt = FMT_BGR if is_color else FMT_GRAY
         self.optimize = bool(optimize)
@@ -460,15 +481,44 @@ class JpegEncoder(Handle):
         self._out = None
         flags = (DVC_FLAG_JPEG_OPT_HUFFMAN if self.optimize else 0) | (DVC_FLAG_DEVICE_PTRS if device_ptrs else 0) \
             | (DVC_FLAG_JOIN_STREAM if stream is not None else 0)
-        self._create(lib().dvc_jpeg_create, self.W, self.H, self.fmt, int(quality), self.max_batch,
-                     self.device, ctypes.c_void_p(int(stream)) if stream is not None else None, flags)
+        hs = ctypes.c_void_p(int(stream)) if stream is not None else None
+        if self.target_bytes is None:
+            self._create(lib().dvc_jpeg_create, self.W, self.H, self.fmt, int(quality), self.max_batch, self.device, hs,
+                         flags)
+        else:
+            if not hasattr(lib(), "dvc_jpeg_create_rate"):
+                raise DvcError(DVC_E_UNSUPPORTED, "the loaded library has no dvc_jpeg_create_rate")
+            if self.target_bytes < 0:
+                raise ValueError(f"target_bytes {self.target_bytes} is negative")
+            self._create(lib().dvc_jpeg_create_rate, self.W, self.H, self.fmt, self.target_bytes, *self.quality_range,
+                         self.max_batch, self.device, hs, flags)
         h, n = self._h, ctypes.c_size_t()
         check(lib().dvc_jpeg_header(h, None, 0, ctypes.byref(n)))
         buf = (ctypes.c_uint8 * n.value)()
         check(lib().dvc_jpeg_header(h, buf, n.value, ctypes.byref(n)))
         self.header = bytes(buf)
         check(lib().dvc_jpeg_bound(self.W, self.H, self.fmt, ctypes.byref(n)))
-        self.bound = int(n.value) + (JPEG_OPT_PREFIX_MAX if self.optimize else 0)
+        self.bound = int(n.value) + (JPEG_RATE_PREFIX_MAX if self.target_bytes is not None else
+                                     JPEG_OPT_PREFIX_MAX if self.optimize else 0)
+
+    def rate_stats(self) -> dict:
+        """dvc_jpeg_rate_stats: the cumulative counters of a ``target_bytes`` encoder
+        (waits for the handle's stream)."""
+        if not hasattr(lib(), "dvc_jpeg_rate_stats"):
+            raise DvcError(DVC_E_UNSUPPORTED, "the loaded library has no dvc_jpeg_rate_stats")
+        if self._h is None and getattr(self, "_closed_stats", None) is not None:
+            return dict(self._closed_stats)      # (a closed encoder still tells what it did)
+        buf = (ctypes.c_uint64 * len(JPEG_RATE_STATS))()
+        check(lib().dvc_jpeg_rate_stats(self._h, buf))
+        return dict(zip(JPEG_RATE_STATS, (int(v) for v in buf)))
+
+    def close(self) -> None:
+        if self._h is not None and getattr(self, "target_bytes", None) is not None and self.device >= 0:
+            try:
+                self._closed_stats = self.rate_stats()
+            except DvcError:
+                pass
+        super().close()
 
     def tables(self, counts) -> bytes:
         """dvc_jpeg_opt_tables: the DHT segment the encoder would write for the symbol

@@ -9,6 +9,7 @@
 
 #include "../../include/dvc.h"
 #include "../../include/dvc_jpeg_opt.h"
+#include "../../include/dvc_jpeg_rate.h"
 #include "../../include/dvc_jpeg_stream.h"
 #include "host_common.h"
 #include "jpeg_kernels.h"
@@ -42,8 +43,7 @@ uint64_t frame_bound(const dvc::JpegGeom& g) { return (uint64_t)g.nseg * ((uint6
 
 void quant_table(const uint8_t* base, int quality, uint16_t* q)
 {
-    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-    for (int i = 0; i < 64; ++i) q[i] = (uint16_t)std::min(255, std::max(1, (base[i] * s + 50) / 100));
+    for (int i = 0; i < 64; ++i) q[i] = dvc::rate_quant(base[i], quality);
 }
 
 // Canonical codes from a DHT's BITS / HUFFVAL, as a decoder derives them.
@@ -75,12 +75,13 @@ void put16(std::vector<uint8_t>& v, unsigned x)
 }
 
 // SOI, APP0 JFIF, 2 x DQT, SOF0, 2 x DHT, DRI, SOS header; with optimised
-// tables the DHT and SOS segments are not here but in front of every frame.
-std::vector<uint8_t> make_header(const dvc::JpegGeom& g, const dvc::JpegTables& t, bool opt)
+// tables the DHT and SOS segments are not here but in front of every frame, and
+// on a rate handle the DQT and SOS segments.
+std::vector<uint8_t> make_header(const dvc::JpegGeom& g, const dvc::JpegTables& t, bool opt, bool rate = false)
 {
     using namespace dvc_jpeg_tab;
     std::vector<uint8_t> v = {0xff, 0xd8, 0xff, 0xe0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-    for (int id = 0; id < 2; ++id) {
+    for (int id = 0; id < 2 && !rate; ++id) {
         v.insert(v.end(), {0xff, 0xdb, 0, 67, (uint8_t)id});
         for (int k = 0; k < 64; ++k) v.push_back((uint8_t)t.q[id][kZigzag[k]]);
     }
@@ -107,7 +108,7 @@ std::vector<uint8_t> make_header(const dvc::JpegGeom& g, const dvc::JpegTables& 
     }
     v.insert(v.end(), {0xff, 0xdd, 0, 4});
     put16(v, g.mcus_x);
-    if (opt) return v;
+    if (opt || rate) return v;
     v.insert(v.end(), {0xff, 0xda});
     put16(v, 6 + 2 * nc);
     v.push_back((uint8_t)nc);
@@ -141,12 +142,15 @@ struct dvc_jpeg {
     uint64_t* d_carry = nullptr;
     uint8_t* d_sout = nullptr;
     uint64_t* d_offs = nullptr;
+    // rate handles (dvc_jpeg_create_rate): b.rate is set, the search has `rounds` rounds
+    int rounds = 0;
 };
 
 namespace {
 
 // One launch group (m <= max_batch frames, one table group) up to its packed
-// segments: frames [staged ->] levels -> [tables ->] boff, segbits -> scratch, seglen.
+// segments: frames [staged ->] levels -> [tables ->] boff, segbits -> scratch, seglen;
+// on a rate handle frames -> coef -> the group's quality -> levels.
 int pack_group(dvc_jpeg* h, const uint8_t* in, size_t pitch, size_t frame_stride, int m)
 {
     const dvc::JpegGeom& g = h->g;
@@ -160,6 +164,13 @@ int pack_group(dvc_jpeg* h, const uint8_t* in, size_t pitch, size_t frame_stride
         kfs = h->ip * g.H;
     }
     HIP_OK(dvc::jpeg_launch_dct(kd, kp, kfs, m, g, h->d_tab, h->b, st));
+    if (h->b.rate) {   // the same launches whatever the data: the search runs on the device
+        for (int r = 0; r < h->rounds; ++r) {
+            HIP_OK(dvc::jpeg_launch_rate_bits(m, g, h->d_tab, h->b, st));
+            HIP_OK(dvc::jpeg_launch_rate_step(m, r, h->rounds, g, h->d_tab, h->b, st));
+        }
+        HIP_OK(dvc::jpeg_launch_quant(m, g, h->d_tab, h->b, st));
+    }
     if (h->b.opt) {   // this run of frames is one table group
         HIP_OK(dvc::jpeg_launch_hist(m, g, h->b, st));
         HIP_OK(dvc::jpeg_launch_huff_build(g, h->b, st));
@@ -182,19 +193,26 @@ int dvc_jpeg_bound(int width, int height, int fmt, size_t* bytes)
     return DVC_OK;
 }
 
-int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, int device, void* hip_stream,
-                    uint32_t flags, dvc_jpeg** out)
+namespace {
+
+// dvc_jpeg_create (target_bytes 0: one quality = q_min = q_max) and dvc_jpeg_create_rate.
+int create(int width, int height, int fmt, size_t target_bytes, int q_min, int q_max, int max_batch, int device,
+           void* hip_stream, uint32_t flags, dvc_jpeg** out)
 {
+    const bool rate = target_bytes != 0;
+    const int quality = q_min;
     if (!out) return fail(DVC_E_INVALID, "NULL argument");
     if (fmt == DVC_FMT_I420 || fmt == DVC_FMT_NV12)
         return fail(DVC_E_UNSUPPORTED, "the encoder takes DVC_FMT_BGR or DVC_FMT_GRAY frames (JFIF is full-range)");
     dvc::JpegGeom g{};
     if (!geometry(width, height, fmt, &g)) return fail(DVC_E_INVALID, "frame %dx%d format %d invalid", width, height, fmt);
-    if (quality < 1 || quality > 100) return fail(DVC_E_INVALID, "quality %d outside 1..100", quality);
+    if (!rate && (quality < 1 || quality > 100)) return fail(DVC_E_INVALID, "quality %d outside 1..100", quality);
+    if (rate && (q_min < 1 || q_max > 100 || q_min > q_max))
+        return fail(DVC_E_INVALID, "quality range %d..%d outside 1 <= q_min <= q_max <= 100", q_min, q_max);
     if (max_batch < 0 || max_batch > DVC_MAX_BATCH) return fail(DVC_E_INVALID, "max_batch %d outside 1..%d", max_batch,
                                                                 DVC_MAX_BATCH);
     const bool opt = flags & DVC_FLAG_JPEG_OPT_HUFFMAN;
-    const uint64_t bound = frame_bound(g) + (opt ? DVC_JPEG_OPT_PREFIX_MAX : 0);   // what a frame's slot may need
+    const uint64_t bound = frame_bound(g) + (rate ? DVC_JPEG_RATE_PREFIX_MAX : opt ? DVC_JPEG_OPT_PREFIX_MAX : 0);   // what a frame's slot may need
     if (bound > 0x7fffffffull) return fail(DVC_E_UNSUPPORTED, "frame %dx%d too large", width, height);
     dvc_jpeg* h = new dvc_jpeg();
     h->g = g;
@@ -204,7 +222,8 @@ int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, 
     h->chan = g.gray ? 1 : 3;
     h->bound = bound;
     fill_tables(quality, &h->tab);
-    h->header = make_header(g, h->tab, opt);
+    h->header = make_header(g, h->tab, opt, rate);
+    h->rounds = rate ? dvc::rate_rounds(q_min, q_max) : 0;
     *out = h;
     if (device < 0) return DVC_OK;   // host-only handle: dvc_jpeg_header alone
     *out = nullptr;
@@ -228,6 +247,21 @@ int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, 
         e = mem.alloc(&h->b.counts, dvc::kHuffTables * 256 * sizeof(unsigned long long));
         if (e == hipSuccess) e = mem.alloc(&h->b.opt, sizeof(dvc::JpegOptTables));
         if (e == hipSuccess) e = hipMemset(h->b.opt, 0, sizeof(dvc::JpegOptTables));
+        if (e == hipSuccess) h->b.prefix = {h->b.opt->prefix, &h->b.opt->prefix_len, (uint32_t)dvc::kHuffPrefixCap};
+    }
+    if (e == hipSuccess && rate) {
+        dvc::JpegRateState rs{};
+        rs.target = target_bytes;
+        rs.q_min = q_min;
+        rs.q_max = q_max;
+        rs.frame_fixed = (uint32_t)make_header(g, h->tab, false).size();
+        std::memcpy(rs.base[0], dvc_jpeg_tab::kBaseLuma, 64);
+        std::memcpy(rs.base[1], dvc_jpeg_tab::kBaseChroma, 64);
+        dvc::rate_search_begin(&rs.search, q_min);
+        e = mem.alloc(&h->b.coef, mb * nblk * 64 * sizeof(int16_t));
+        if (e == hipSuccess) e = mem.alloc(&h->b.rate, sizeof(dvc::JpegRateState));
+        if (e == hipSuccess) e = hipMemcpy(h->b.rate, &rs, sizeof(rs), hipMemcpyHostToDevice);
+        if (e == hipSuccess) h->b.prefix = {h->b.rate->prefix, &h->b.rate->prefix_len, (uint32_t)dvc::kRatePrefixCap};
     }
     if (e == hipSuccess && !(flags & DVC_FLAG_DEVICE_PTRS)) {
         e = mem.alloc(&h->d_in, mb * h->ip * g.H);   // staged frames
@@ -239,6 +273,32 @@ int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, 
         return dvc_host::create_failed(e, "jpeg create");
     }
     *out = h;
+    return DVC_OK;
+}
+
+}  // namespace
+
+int dvc_jpeg_create(int width, int height, int fmt, int quality, int max_batch, int device, void* hip_stream,
+                    uint32_t flags, dvc_jpeg** out)
+{
+    return create(width, height, fmt, 0, quality, quality, max_batch, device, hip_stream, flags, out);
+}
+
+int dvc_jpeg_create_rate(int width, int height, int fmt, size_t target_bytes, int q_min, int q_max, int max_batch,
+                         int device, void* hip_stream, uint32_t flags, dvc_jpeg** out)
+{
+    if (!target_bytes) return fail(DVC_E_INVALID, "a target of 0 bytes a frame");
+    return create(width, height, fmt, target_bytes, q_min, q_max, max_batch, device, hip_stream, flags, out);
+}
+
+int dvc_jpeg_rate_stats(dvc_jpeg* h, struct dvc_jpeg_rate_stats* out)
+{
+    if (!h || !out) return fail(DVC_E_INVALID, "NULL argument");
+    if (h->device < 0 || !h->b.rate) return fail(DVC_E_STATE, "the counters need a device handle of dvc_jpeg_create_rate");
+    static_assert(sizeof(struct dvc_jpeg_rate_stats) == sizeof(dvc::RateStats), "the counters' layout");
+    HIP_OK(hipSetDevice(h->device));
+    HIP_OK(hipStreamSynchronize(h->stream.s));
+    HIP_OK(hipMemcpy(out, &h->b.rate->stats, sizeof(*out), hipMemcpyDeviceToHost));
     return DVC_OK;
 }
 
@@ -402,7 +462,7 @@ int dvc_jpeg_opt_tables(dvc_jpeg* h, const uint64_t* counts, uint8_t* dht, size_
     uint32_t len = 0;
     std::vector<uint8_t> prefix(sizeof(d->prefix));
     HIP_OK(hipMemcpyAsync(h->b.counts, counts, dvc::kHuffTables * 256 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_OK(dvc::jpeg_launch_huff_build(h->g, h->b, st));
+    HIP_OK(dvc::jpeg_launch_huff_build(h->g, h->b, st, false));   // into the tables' own prefix
     HIP_OK(hipMemcpyAsync(&len, &d->prefix_len, sizeof(len), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(prefix.data(), d->prefix, prefix.size(), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "jpeg_huff_core.h"
+#include "jpeg_rate_core.h"
 #include "jpeg_stream_core.h"
 
 namespace dvc {
@@ -35,6 +36,31 @@ struct JpegOptTables {
     uint8_t prefix[(kHuffPrefixCap + 3) & ~3];
 };
 
+// The bytes in front of every frame of a group (NULL bytes: none): the DHT + SOS
+// of optimised tables, or a rate handle's DQT, DQT, [DHT,] SOS. `len` is
+// written on the device by the kernels that build the bytes.
+struct JpegPrefix {
+    const uint8_t* bytes;
+    const uint32_t* len;
+    uint32_t cap;
+};
+
+// A rate handle's device state (DESIGN.md "Rate target"): what create sets, the
+// running search of the current group, the estimate the round's workgroups add
+// to, the counters, and the group's prefix.
+constexpr int kRatePrefixCap = kRateDqtPairBytes + kHuffPrefixCap;
+struct JpegRateState {
+    unsigned long long est;     // sum of rate_seg_bytes over the round's segments
+    unsigned long long target;  // bytes a frame
+    RateSearch search;
+    RateStats stats;
+    int32_t q_min, q_max;
+    uint32_t frame_fixed;       // a fixed-table sample's bytes in front of its entropy data
+    uint32_t prefix_len;
+    uint8_t base[2][64];        // quantiser base tables, natural order
+    uint8_t prefix[(kRatePrefixCap + 3) & ~3];
+};
+
 // One frame's geometry. A restart segment is one MCU row: `bps` blocks in scan
 // order (colour: Y00 Y01 Y10 Y11 Cb Cr per 16x16 MCU; gray: one 8x8 block per MCU).
 struct JpegGeom {
@@ -58,16 +84,31 @@ struct JpegBufs {
     // optimised tables only (NULL otherwise):
     unsigned long long* counts;   // [4][256]: DC class 0, AC class 0, DC class 1, AC class 1
     JpegOptTables* opt;
+    JpegPrefix prefix;   // what k_jpeg_gather and the stream kernels put in front of a frame
+    // rate handles only (NULL otherwise):
+    int16_t* coef;       // nseg * bps * 64 unquantised coefficients, zigzag order
+    JpegRateState* rate;
 };
 
 // n frames (rows of `pitch` bytes, frames `fstride` apart; BGR or one channel)
-// -> levels.
+// -> levels; on a rate handle (b.rate set) -> coef.
 hipError_t jpeg_launch_dct(const uint8_t* frames, size_t pitch, size_t fstride, int n, const JpegGeom& g,
                            const JpegTables* tab, const JpegBufs& b, hipStream_t st);
 // Optimised tables: levels of the n frames of a group -> counts (zeroed first).
 hipError_t jpeg_launch_hist(int n, const JpegGeom& g, const JpegBufs& b, hipStream_t st);
-// counts -> opt (tables and prefix).
-hipError_t jpeg_launch_huff_build(const JpegGeom& g, const JpegBufs& b, hipStream_t st);
+// counts -> opt (tables), and the DHT + SOS bytes: behind the DQT pair of
+// b.rate's prefix when `group` and b.rate is set, into opt's own prefix otherwise.
+hipError_t jpeg_launch_huff_build(const JpegGeom& g, const JpegBufs& b, hipStream_t st, bool group = true);
+// Rate handles. One round of the search over the n frames of a group: coef at
+// the state's quality -> the state's estimate (nothing once the search ended).
+hipError_t jpeg_launch_rate_bits(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st);
+// The search step behind round `round`; the last of `rounds` also leaves the
+// chosen quantiser in tab, the DQT pair (and the SOS, without b.opt) in the
+// prefix, the counters, and the search ready for the next group.
+hipError_t jpeg_launch_rate_step(int n, int round, int rounds, const JpegGeom& g, JpegTables* tab, const JpegBufs& b,
+                                 hipStream_t st);
+// coef -> levels with tab's quantiser.
+hipError_t jpeg_launch_quant(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st);
 // The three below read b.opt's tables when it is set and `tab`'s fixed ones otherwise.
 // levels -> boff, segbits.
 hipError_t jpeg_launch_bits(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st);

@@ -4,6 +4,9 @@
 // DESIGN.md "Motion-JPEG stream" is the normative text of the arithmetic.
 //
 //   k_jpeg_dct     BGR / gray -> YCbCr, 4:2:0, integer DCT, quantise, zigzag
+//   k_jpeg_rate_bits, k_jpeg_rate_step, k_jpeg_quant  rate handles: coefficients kept
+//                  unquantised, a search for the group's quality over their exact
+//                  coded size, then the levels at that quality (jpeg_rate_core.h)
 //   k_jpeg_bits    per-block code lengths, bit offsets along each restart segment
 //   k_jpeg_pack    codes OR-ed into an LDS bit buffer, 0xFF stuffing -> scratch
 //   k_jpeg_gather  segments + RST markers + EOI -> the frame's output slot
@@ -76,7 +79,8 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w, u
 // 256 threads = 4 waves, one work unit each: a 16x16 MCU (colour, 6 blocks) or
 // four 8x8 blocks side by side (gray). A lane loads 4 pixels of one row (three
 // aligned dwords of BGR, or one of gray), clamped to the frame edge.
-template <bool GRAY>
+// RAW (rate handles): the coefficients themselves, not their levels, go out.
+template <bool GRAY, bool RAW>
 __global__ __launch_bounds__(256) void k_jpeg_dct(const uint8_t* __restrict__ frames, size_t pitch, size_t fstride,
                                                   JpegGeom g, const JpegTables* __restrict__ tab,
                                                   int16_t* __restrict__ levels, int aligned)
@@ -89,7 +93,7 @@ __global__ __launch_bounds__(256) void k_jpeg_dct(const uint8_t* __restrict__ fr
     __shared__ uint16_t s_q[128];
     __shared__ uint8_t s_zpos[64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (threadIdx.x < 128) s_q[threadIdx.x] = (&tab->q[0][0])[threadIdx.x];
+    if (!RAW && threadIdx.x < 128) s_q[threadIdx.x] = (&tab->q[0][0])[threadIdx.x];
     if (threadIdx.x < 64) s_zpos[threadIdx.x] = tab->zpos[threadIdx.x];
     const int units = g.units_x * g.nseg;
     int unit = blockIdx.x * 4 + wave;
@@ -175,6 +179,10 @@ __global__ __launch_bounds__(256) void k_jpeg_dct(const uint8_t* __restrict__ fr
 #pragma unroll
         for (int v = 0; v < 8; ++v) {
             const int nat = v * 8 + i8;
+            if (RAW) {   // |F| < 2^15: rate_coef_bound, run by tools/jpeg_rate_host_check.cc
+                s_lv[wave][blk * 64 + s_zpos[nat]] = (int16_t)o[v];
+                continue;
+            }
             const int Q = q[nat], F = o[v];
             int l = (int)((uint32_t)(abs(F) + (Q >> 1)) / (uint32_t)Q);
             if (nat) l = min(l, 1023);
@@ -309,6 +317,121 @@ __global__ __launch_bounds__(256) void k_jpeg_bits(JpegGeom g, const JpegTables*
         carry += tot;
     }
     if (t == 0) segbits[seg] = carry;
+}
+
+// ---- rate target: k_jpeg_rate_bits, k_jpeg_rate_step, k_jpeg_quant ------------------
+// The block whose DC is block j's predictor (dc_pred's rule), -1 for none.
+__device__ __forceinline__ int dc_pred_block(int j, int gray)
+{
+    if (gray) return j - 1;
+    const int b = j % 6;
+    return b == 0 ? j - 3 : (b < 4 ? j - 1 : j - 6);
+}
+
+// One round of the search, k_jpeg_bits' geometry: a workgroup per (segment,
+// frame), a wave per block, a lane per coefficient. The two quantisers of the
+// round's quality are built in LDS in zigzag order; a lane quantises its
+// coefficient (lane 0 also the predecessor's DC) and sizes its code with the
+// fixed tables; the segment's bits become bytes and go to the estimate with one
+// atomic a workgroup. Integer sums: the order of the atomics does not matter.
+__global__ __launch_bounds__(256) void k_jpeg_rate_bits(JpegGeom g, const JpegTables* __restrict__ tab,
+                                                        const int16_t* __restrict__ coef,
+                                                        JpegRateState* __restrict__ rs)
+{
+    __shared__ uint32_t s_dc[12], s_ac[256], s_w[4];
+    __shared__ uint16_t s_q[2][64];
+    if (!rs->search.active) return;   // (the same in every thread: k_jpeg_rate_step wrote it before this launch)
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int quality = rs->search.q;
+    s_ac[t] = tab->ac[t];
+    if (t < 12) s_dc[t] = tab->dc[t];
+    if (t < 128) s_q[t >> 6][tab->zpos[t & 63] & 63] = rate_quant(rs->base[t >> 6][t & 63], quality);
+    __syncthreads();
+    const size_t seg = (size_t)blockIdx.y * g.nseg + blockIdx.x;
+    const int16_t* cf = coef + seg * g.bps * 64;
+    const int zrl = (int)(s_ac[0xF0] >> 16);
+    uint32_t bits = 0;   // of this wave's blocks (the same in all its lanes)
+    for (int j = wave; j < g.bps; j += 4) {
+        const uint16_t* q = s_q[block_class(j, g.gray)];
+        const int lv = rate_level(cf[(size_t)j * 64 + lane], q[lane], lane > 0);
+        int pred = 0;
+        if (lane == 0) {
+            const int p = dc_pred_block(j, g.gray);
+            if (p >= 0) pred = rate_level(cf[(size_t)p * 64], q[0], false);
+        }
+        const LaneCode c = lane_code(lv, lane, pred, s_dc, s_ac);
+        uint32_t n = (uint32_t)(c.nzrl * zrl + c.n);
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) n += __shfl_xor(n, d, 64);
+        bits += n;
+    }
+    if (lane == 0) s_w[wave] = bits;
+    __syncthreads();
+    if (t == 0) atomicAdd(&rs->est, (unsigned long long)rate_seg_bytes(s_w[0] + s_w[1] + s_w[2] + s_w[3]));
+}
+
+// Behind every round: thread 0 applies the search step to the round's estimate
+// and clears it. Behind the last round the 128 threads also leave the chosen
+// quality's quantiser in tab->q and its DQT pair in the group's prefix (the SOS
+// behind them when `sos`: fixed tables; k_jpeg_huff_build appends DHT + SOS
+// otherwise), and thread 0 the counters and the next group's search.
+__global__ __launch_bounds__(128) void k_jpeg_rate_step(JpegRateState* __restrict__ rs, JpegTables* __restrict__ tab,
+                                                        uint32_t m, int round, int last, int nc, int sos)
+{
+    __shared__ int s_quality;
+    const int t = threadIdx.x;
+    if (t == 0) {
+        const uint64_t budget = (uint64_t)m * rs->target;
+        RateSearch s = rs->search;
+        rate_search_step(&s, round, rs->q_max, rate_estimate(m, rs->frame_fixed, rs->est), budget);
+        rs->est = 0ull;
+        s_quality = s.lo;
+        if (last) {
+            rate_stats_add(&rs->stats, s, m, budget);
+            rate_search_begin(&s, rs->q_min);
+        }
+        rs->search = s;
+    }
+    if (!last) return;
+    __syncthreads();
+    const int id = t >> 6, i = t & 63;
+    const uint16_t q = rate_quant(rs->base[id][i], s_quality);
+    uint8_t* d = rs->prefix + id * kRateDqtBytes;
+    tab->q[id][i] = q;
+    d[5 + (tab->zpos[i] & 63)] = (uint8_t)q;
+    if (i < 5) d[i] = rate_dqt_head(i, id);
+    if (t == 0) {
+        int len = kRateDqtPairBytes;
+        if (sos) {   // the fixed tables' SOS: every component on tables 0
+            len = huff_put_sos(rs->prefix, len, nc);
+            for (int c = 0; c < 3; ++c)
+                if (c < nc) rs->prefix[kRateDqtPairBytes + 6 + 2 * c] = 0x00;
+        }
+        rs->prefix_len = (uint32_t)len;
+    }
+}
+
+// coef -> levels at tab's quantiser (what k_jpeg_dct stores at a fixed quality):
+// a thread takes eight coefficients of one block, 16 bytes in and out.
+__global__ __launch_bounds__(256) void k_jpeg_quant(const JpegTables* __restrict__ tab, const int16_t* __restrict__ coef,
+                                                    int16_t* __restrict__ levels, size_t nvec, int gray)
+{
+    __shared__ uint16_t s_q[2][64];
+    const int t = threadIdx.x;
+    if (t < 128) s_q[t >> 6][tab->zpos[t & 63] & 63] = tab->q[t >> 6][t & 63];
+    __syncthreads();
+    const size_t v = (size_t)blockIdx.x * 256 + t;
+    if (v >= nvec) return;
+    const uint16_t* q = s_q[block_class((int)((v >> 3) % 6), gray)];   // (a segment's blocks are a multiple of 6 in colour)
+    const int k0 = (int)(v & 7) * 8;
+    union {
+        uint4 u;
+        int16_t h[8];
+    } x;
+    x.u = reinterpret_cast<const uint4*>(coef)[v];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x.h[i] = (int16_t)rate_level(x.h[i], q[k0 + i], k0 + i > 0);
+    reinterpret_cast<uint4*>(levels)[v] = x.u;
 }
 
 // ---- k_jpeg_pack ------------------------------------------------------------------
@@ -483,8 +606,11 @@ __device__ __forceinline__ HuffKey huff_shfl_xor(const HuffKey& k, int d)
     return HuffKey{__shfl_xor(k.f, d, 64), __shfl_xor(k.i, d, 64)};
 }
 
+// The DHT + SOS bytes go to pdst + base and base + their length to *plen_dst: the
+// tables' own prefix (base 0), or a rate handle's behind its DQT pair.
 __global__ __launch_bounds__(256) void k_jpeg_huff_build(const unsigned long long* __restrict__ counts, int nc,
-                                                         JpegOptTables* __restrict__ out)
+                                                         JpegOptTables* __restrict__ out, uint8_t* __restrict__ pdst,
+                                                         uint32_t* __restrict__ plen_dst, uint32_t base)
 {
     __shared__ uint16_t s_size[kHuffTables][kHuffSyms + 1];
     __shared__ uint32_t s_cnt[kHuffTables][kHuffMaxDepth + 2];
@@ -578,26 +704,26 @@ __global__ __launch_bounds__(256) void k_jpeg_huff_build(const unsigned long lon
         if (t < 12) out->dc[k][t] = s_code[2 * k][t];
     }
     const int plen = s_plen;
-    for (int i = t; i < plen; i += 256) out->prefix[i] = s_prefix[i];
-    if (t == 0) out->prefix_len = (uint32_t)plen;
+    for (int i = t; i < plen; i += 256) pdst[base + i] = s_prefix[i];
+    if (t == 0) *plen_dst = base + (uint32_t)plen;
 }
 
 // ---- k_jpeg_gather ----------------------------------------------------------------
 // One workgroup per (segment, frame): the segment's place is the sum of the
 // lengths before it plus their 2-byte RST markers; the last segment is followed
-// by EOI. A frame that does not fit its slot is not written at all. opt (may be
-// NULL): the group's DHT + SOS prefix goes in front of every frame's first
-// segment and counts in its size.
+// by EOI. A frame that does not fit its slot is not written at all. prefix (its
+// bytes may be NULL): the group's table segments go in front of every frame's
+// first segment and count in its size.
 __global__ __launch_bounds__(256) void k_jpeg_gather(JpegGeom g, const uint8_t* __restrict__ scratch,
                                                      const uint32_t* __restrict__ seglen,
-                                                     const JpegOptTables* __restrict__ opt, uint8_t* __restrict__ out,
+                                                     JpegPrefix prefix, uint8_t* __restrict__ out,
                                                      size_t out_stride, uint32_t* __restrict__ sizes,
                                                      uint32_t* __restrict__ overflow)
 {
     __shared__ uint32_t s_w[4];
     const int t = threadIdx.x, s = blockIdx.x;
     const uint32_t* sl = seglen + (size_t)blockIdx.y * g.nseg;
-    const uint32_t plen = opt ? min(opt->prefix_len, (uint32_t)kHuffPrefixCap) : 0u;
+    const uint32_t plen = prefix.bytes ? min(*prefix.len, prefix.cap) : 0u;
     uint32_t before = 0, all = 0;
     for (int i = t; i < g.nseg; i += 256) {
         const uint32_t n = sl[i] + 2u;   // its RST marker, or EOI after the last
@@ -621,7 +747,7 @@ __global__ __launch_bounds__(256) void k_jpeg_gather(JpegGeom g, const uint8_t* 
     for (uint32_t i = t; i < len; i += 256) dst[i] = src[i];
     if (s == 0) {
         uint8_t* head = out + (size_t)blockIdx.y * out_stride;
-        for (uint32_t i = t; i < plen; i += 256) head[i] = opt->prefix[i];
+        for (uint32_t i = t; i < plen; i += 256) head[i] = prefix.bytes[i];
     }
     if (t == 0) {
         dst[len] = 0xff;
@@ -638,7 +764,7 @@ __global__ __launch_bounds__(256) void k_jpeg_gather(JpegGeom g, const uint8_t* 
 // frame's segments, then one thread runs the exclusive prefix behind the carry
 // of the groups before (*carry; 0 when `first`) and leaves this group's end there.
 __global__ __launch_bounds__(256) void k_jpeg_stream_offsets(JpegGeom g, const uint32_t* __restrict__ seglen,
-                                                             const JpegOptTables* __restrict__ opt,
+                                                             JpegPrefix prefix,
                                                              uint32_t header_len, int m, int first, uint64_t cap,
                                                              uint64_t* __restrict__ carry,
                                                              uint64_t* __restrict__ offsets,
@@ -646,7 +772,7 @@ __global__ __launch_bounds__(256) void k_jpeg_stream_offsets(JpegGeom g, const u
 {
     __shared__ uint64_t s_need[kJpegStreamMaxGroup];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t plen = opt ? min(opt->prefix_len, (uint32_t)kHuffPrefixCap) : 0u;
+    const uint32_t plen = prefix.bytes ? min(*prefix.len, prefix.cap) : 0u;
     for (int f = wave; f < m; f += 4) {
         uint32_t sum = (uint32_t)stream_seg_sum(seglen + (size_t)f * g.nseg, g.nseg, lane, 64);
 #pragma unroll
@@ -667,8 +793,7 @@ __global__ __launch_bounds__(256) void k_jpeg_stream_offsets(JpegGeom g, const u
 // workgroup also writes the header and the prefix. A sample that does not lie
 // inside `cap` is not written.
 __global__ __launch_bounds__(256) void k_jpeg_stream_gather(JpegGeom g, const uint8_t* __restrict__ scratch,
-                                                            const uint32_t* __restrict__ seglen,
-                                                            const JpegOptTables* __restrict__ opt,
+                                                            const uint32_t* __restrict__ seglen, JpegPrefix prefix,
                                                             const uint8_t* __restrict__ header, uint32_t header_len,
                                                             const uint64_t* __restrict__ offsets,
                                                             const uint64_t* __restrict__ rebase, uint64_t cap,
@@ -678,7 +803,7 @@ __global__ __launch_bounds__(256) void k_jpeg_stream_gather(JpegGeom g, const ui
     const int t = threadIdx.x, s = blockIdx.x, f = blockIdx.y;
     if (!stream_fits(offsets[f + 1], cap)) return;
     const uint32_t* sl = seglen + (size_t)f * g.nseg;
-    const uint32_t plen = opt ? min(opt->prefix_len, (uint32_t)kHuffPrefixCap) : 0u;
+    const uint32_t plen = prefix.bytes ? min(*prefix.len, prefix.cap) : 0u;
     uint32_t before;
     (void)block_excl_scan((uint32_t)stream_seg_sum(sl, s, t, 256), s_w, &before);
     uint8_t* sample = out + (offsets[f] - (rebase ? *rebase : 0ull));
@@ -688,7 +813,7 @@ __global__ __launch_bounds__(256) void k_jpeg_stream_gather(JpegGeom g, const ui
     for (uint32_t i = t; i < len; i += 256) dst[i] = src[i];
     if (s == 0) {
         for (uint32_t i = t; i < header_len; i += 256) sample[i] = header[i];
-        for (uint32_t i = t; i < plen; i += 256) sample[header_len + i] = opt->prefix[i];
+        for (uint32_t i = t; i < plen; i += 256) sample[header_len + i] = prefix.bytes[i];
     }
     if (t == 0) {
         dst[len] = 0xff;
@@ -703,10 +828,20 @@ hipError_t jpeg_launch_dct(const uint8_t* frames, size_t pitch, size_t fstride, 
 {
     const int aligned = pitch % 4 == 0 && ((uintptr_t)frames & 3) == 0 && (n <= 1 || fstride % 4 == 0);
     const dim3 grid((unsigned)((g.units_x * g.nseg + 3) / 4), (unsigned)n);
-    if (g.gray)
-        hipLaunchKernelGGL(k_jpeg_dct<true>, grid, dim3(256), 0, st, frames, pitch, fstride, g, tab, b.levels, aligned);
-    else
-        hipLaunchKernelGGL(k_jpeg_dct<false>, grid, dim3(256), 0, st, frames, pitch, fstride, g, tab, b.levels, aligned);
+    if (b.rate) {
+        if (g.gray)
+            hipLaunchKernelGGL((k_jpeg_dct<true, true>), grid, dim3(256), 0, st, frames, pitch, fstride, g, tab, b.coef,
+                               aligned);
+        else
+            hipLaunchKernelGGL((k_jpeg_dct<false, true>), grid, dim3(256), 0, st, frames, pitch, fstride, g, tab, b.coef,
+                               aligned);
+    } else if (g.gray) {
+        hipLaunchKernelGGL((k_jpeg_dct<true, false>), grid, dim3(256), 0, st, frames, pitch, fstride, g, tab, b.levels,
+                           aligned);
+    } else {
+        hipLaunchKernelGGL((k_jpeg_dct<false, false>), grid, dim3(256), 0, st, frames, pitch, fstride, g, tab, b.levels,
+                           aligned);
+    }
     return hipGetLastError();
 }
 
@@ -718,9 +853,36 @@ hipError_t jpeg_launch_hist(int n, const JpegGeom& g, const JpegBufs& b, hipStre
     return hipGetLastError();
 }
 
-hipError_t jpeg_launch_huff_build(const JpegGeom& g, const JpegBufs& b, hipStream_t st)
+hipError_t jpeg_launch_huff_build(const JpegGeom& g, const JpegBufs& b, hipStream_t st, bool group)
 {
-    hipLaunchKernelGGL(k_jpeg_huff_build, dim3(1), dim3(256), 0, st, b.counts, g.gray ? 1 : 3, b.opt);
+    if (group && b.rate)
+        hipLaunchKernelGGL(k_jpeg_huff_build, dim3(1), dim3(256), 0, st, b.counts, g.gray ? 1 : 3, b.opt, b.rate->prefix,
+                           &b.rate->prefix_len, (uint32_t)kRateDqtPairBytes);
+    else
+        hipLaunchKernelGGL(k_jpeg_huff_build, dim3(1), dim3(256), 0, st, b.counts, g.gray ? 1 : 3, b.opt, b.opt->prefix,
+                           &b.opt->prefix_len, 0u);
+    return hipGetLastError();
+}
+
+hipError_t jpeg_launch_rate_bits(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_jpeg_rate_bits, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, tab, b.coef, b.rate);
+    return hipGetLastError();
+}
+
+hipError_t jpeg_launch_rate_step(int n, int round, int rounds, const JpegGeom& g, JpegTables* tab, const JpegBufs& b,
+                                 hipStream_t st)
+{
+    hipLaunchKernelGGL(k_jpeg_rate_step, dim3(1), dim3(128), 0, st, b.rate, tab, (uint32_t)n, round,
+                       (int)(round == rounds - 1), g.gray ? 1 : 3, (int)(b.opt == nullptr));
+    return hipGetLastError();
+}
+
+hipError_t jpeg_launch_quant(int n, const JpegGeom& g, const JpegTables* tab, const JpegBufs& b, hipStream_t st)
+{
+    const size_t nvec = (size_t)n * g.nseg * g.bps * 8;
+    hipLaunchKernelGGL(k_jpeg_quant, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, st, tab, b.coef, b.levels, nvec,
+                       g.gray);
     return hipGetLastError();
 }
 
@@ -750,7 +912,7 @@ hipError_t jpeg_launch_gather(int n, const JpegGeom& g, const JpegBufs& b, uint8
                               uint32_t* sizes, hipStream_t st)
 {
     hipLaunchKernelGGL(k_jpeg_gather, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, b.scratch, b.seglen,
-                       b.opt, out, out_stride, sizes, b.overflow);
+                       b.prefix, out, out_stride, sizes, b.overflow);
     return hipGetLastError();
 }
 
@@ -759,12 +921,12 @@ hipError_t jpeg_launch_stream(int n, int first, const JpegGeom& g, const JpegBuf
                               uint8_t* out, uint64_t cap, hipStream_t st)
 {
     if (n < 1 || n > kJpegStreamMaxGroup) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_jpeg_stream_offsets, dim3(1), dim3(256), 0, st, g, b.seglen, b.opt, header_len, n, first, cap,
+    hipLaunchKernelGGL(k_jpeg_stream_offsets, dim3(1), dim3(256), 0, st, g, b.seglen, b.prefix, header_len, n, first, cap,
                        carry, offsets, b.overflow);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_jpeg_stream_gather, dim3((unsigned)g.nseg, (unsigned)n), dim3(256), 0, st, g, b.scratch,
-                       b.seglen, b.opt, header, header_len, offsets, rebase, cap, out);
+                       b.seglen, b.prefix, header, header_len, offsets, rebase, cap, out);
     return hipGetLastError();
 }
 

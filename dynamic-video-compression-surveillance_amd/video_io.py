@@ -24,7 +24,10 @@ the accelerated path. Here:
   ISO/IEC 10918-1), every frame a baseline JPEG encoded on the GPU by
   ``dvc_jpeg_encode`` at ``DVC_VIDEO_QUALITY`` (default 75), with the fixed
   Huffman tables or, with ``DVC_VIDEO_HUFFMAN=optimized``, tables built on the
-  GPU for every batch of frames. These are not the
+  GPU for every batch of frames; with ``DVC_VIDEO_BITRATE`` (kbit/s) the
+  quality is not fixed but searched on the GPU for every batch, inside
+  ``DVC_VIDEO_QUALITY_RANGE=lo:hi`` (default 10:95), so that the batch stays
+  under the rate (DESIGN.md "Rate target"). These are not the
   reference's MPEG-4 Part 2 files (intra-only, another codec: sizes are not
   comparable with its), but they are compressed, so the size reduction
   ``performance_analysis`` reports means something;
@@ -42,6 +45,7 @@ the accelerated path. Here:
 from __future__ import annotations
 
 import json
+import logging
 import os
 import struct
 from urllib.parse import parse_qs, urlparse
@@ -326,11 +330,17 @@ class Mp4MjpegWriter:
     batches of ``batch`` (the rest at release) and muxed by :class:`Mp4Muxer`.
     ``encoder``: anything with ``header`` and ``encode(frames) -> [bytes]``
     (default: :class:`_native.JpegEncoder` on ``device``; ``optimize=True``:
-    with Huffman tables built on the GPU for every batch)."""
+    with Huffman tables built on the GPU for every batch). ``bitrate_kbps``:
+    no fixed ``quality`` but a target of ``bitrate_kbps * 125 / fps`` bytes a
+    frame, met batch by batch with a quality of ``quality_range`` (DESIGN.md
+    "Rate target": the target bounds the size before byte stuffing)."""
 
     def __init__(self, path: str, fps: float, size, is_color: bool = True, device: int = 0, quality: int = 75,
-                 batch: int = 8, encoder=None, optimize: bool = False):
+                 batch: int = 8, encoder=None, optimize: bool = False, bitrate_kbps=None, quality_range=(10, 95)):
         self.path, self.W, self.H, self.is_color = path, int(size[0]), int(size[1]), bool(is_color)
+        self.target_bytes = None if bitrate_kbps is None else bitrate_target_bytes(bitrate_kbps, fps)
+        self.quality_range = (int(quality_range[0]), int(quality_range[1]))
+        self._rate_encoders = []
         self.n, self._batch, self._fill = 0, max(1, int(batch)), 0
         self.device, self.quality, self.optimize, self._own_encoder = int(device), int(quality), bool(optimize), \
             encoder is None
@@ -338,7 +348,9 @@ class Mp4MjpegWriter:
             from ._native import JpegEncoder
             # (the keyword only when set: an encoder class put in JpegEncoder's place may know nothing of it)
             opt = {"optimize": True} if optimize else {}
-            encoder = JpegEncoder(self.W, self.H, self.is_color, quality, self._batch, device, **opt)
+            encoder = JpegEncoder(self.W, self.H, self.is_color, quality, self._batch, device, **opt, **self._rate_args())
+            if self.target_bytes is not None and hasattr(encoder, "rate_stats"):
+                self._rate_encoders.append(encoder)
         self._enc = encoder
         self._shape = (self.H, self.W, 3) if self.is_color else (self.H, self.W)
         # the pending batch; the GPU encoder hands out page-locked memory for it
@@ -347,6 +359,11 @@ class Mp4MjpegWriter:
 
     def isOpened(self) -> bool:
         return self._mux is not None
+
+    def _rate_args(self) -> dict:
+        if self.target_bytes is None:
+            return {}
+        return {"target_bytes": self.target_bytes, "quality_range": self.quality_range}
 
     def _flush(self) -> None:
         if self._fill:
@@ -363,8 +380,22 @@ class Mp4MjpegWriter:
         if not self._own_encoder or not hasattr(self._enc, "encode_stream") or \
                 not hasattr(N.lib(), "dvc_jpeg_encode_stream"):
             return None
-        return N.JpegEncoder(self.W, self.H, self.is_color, self.quality, self._batch, self.device,
-                             optimize=self.optimize, device_ptrs=True, stream=stream)
+        enc = N.JpegEncoder(self.W, self.H, self.is_color, self.quality, self._batch, self.device,
+                            optimize=self.optimize, device_ptrs=True, stream=stream, **self._rate_args())
+        if self.target_bytes is not None:
+            self._rate_encoders.append(enc)
+        return enc
+
+    def rate_line(self) -> str:
+        """What the rate target came to, over this writer's encoders (closed ones included)."""
+        st = [e.rate_stats() for e in self._rate_encoders]
+        frames, groups = sum(s["frames"] for s in st), sum(s["groups"] for s in st)
+        sizes = self._mux.sizes if self._mux is not None else []
+        return (f"rate target {self.path}: {self.target_bytes} bytes/frame, quality {self.quality_range[0]}.."
+                f"{self.quality_range[1]}: mean quality {sum(s['quality_frames'] for s in st) / max(frames, 1):.1f}, "
+                f"{sum(s['missed_groups'] for s in st)} of {groups} groups missed, "
+                f"{sum(s['est_bytes'] for s in st) / max(frames, 1):.0f} bytes/frame estimated, "
+                f"{sum(sizes) / max(len(sizes), 1):.0f} written")
 
     def write_samples(self, buffer, offsets) -> None:
         """Frames already encoded (``device_encoder().encode_stream``): complete samples
@@ -391,6 +422,8 @@ class Mp4MjpegWriter:
             return
         try:
             self._flush()
+            if self._rate_encoders:
+                logging.info(self.rate_line())
         finally:
             self._mux.close()
             self._mux = None
@@ -877,6 +910,31 @@ class NpyStreamWriter:
             self._fp = None
 
 
+def bitrate_target_bytes(bitrate_kbps, fps) -> int:
+    """Bytes a frame of ``bitrate_kbps`` kbit/s at ``fps`` frames a second."""
+    return max(1, int(float(bitrate_kbps) * 125 / float(fps)))
+
+
+def _sink_rate_args() -> dict:
+    """DVC_VIDEO_BITRATE (kbit/s, a positive number) and DVC_VIDEO_QUALITY_RANGE=lo:hi -> Mp4MjpegWriter's keywords."""
+    rate, qr = os.environ.get("DVC_VIDEO_BITRATE"), os.environ.get("DVC_VIDEO_QUALITY_RANGE")
+    out = {}
+    if rate is not None:
+        try:
+            out["bitrate_kbps"] = float(rate)
+        except ValueError:
+            out["bitrate_kbps"] = -1.0
+        if not 0 < out["bitrate_kbps"] < float("inf"):
+            raise ValueError(f"DVC_VIDEO_BITRATE={rate!r}: a positive number of kbit/s")
+    if qr is not None:
+        lo, sep, hi = qr.partition(":")
+        if not (sep and lo.isdigit() and hi.isdigit() and 1 <= int(lo) <= int(hi) <= 100):
+            raise ValueError(f"DVC_VIDEO_QUALITY_RANGE={qr!r}: lo:hi with 1 <= lo <= hi <= 100")
+        if rate is not None:
+            out["quality_range"] = (int(lo), int(hi))
+    return out
+
+
 def open_sink(path: str, fps: float, size, is_color: bool = True):
     """cv2.VideoWriter(path, mp4v, fps, size)-like object."""
     root, ext = os.path.splitext(path)
@@ -889,7 +947,7 @@ def open_sink(path: str, fps: float, size, is_color: bool = True):
         if huffman not in ("fixed", "optimized"):
             raise ValueError(f"DVC_VIDEO_HUFFMAN={huffman!r}: fixed or optimized")
         return Mp4MjpegWriter(path, fps, size, is_color, dev, int(os.environ.get("DVC_VIDEO_QUALITY", 75)),
-                              optimize=huffman == "optimized")
+                              optimize=huffman == "optimized", **_sink_rate_args())
     if cv2 is not None and ext != ".npy":
         fourcc = cv2.VideoWriter_fourcc(*"mp4v")
         return cv2.VideoWriter(path, fourcc, fps, tuple(size), isColor=is_color)

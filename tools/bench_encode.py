@@ -8,8 +8,14 @@ each kernel per batch. --huffman optimized: a handle with
 DVC_FLAG_JPEG_OPT_HUFFMAN (tables built on the GPU for every batch); --frames fd:
 the FD worker's compressed frames of the same clip instead of the clip's own.
 The line carries the total bytes per frame, header included, for both modes.
+--target-bytes N: a rate handle (dvc_jpeg_create_rate) with N bytes a frame and
+--quality-range lo:hi (default 10:95) instead of --quality; N = 0 takes the
+size of the same frames at --quality with the fixed tables, header included, so
+that the search ends inside the range. The line then carries the handle's
+counters and the bytes written against the target, stuffing included.
   python tools/bench_encode.py [--kernels] [--out FILE] [--width W --height H --batch B --quality Q]
                                [--huffman fixed|optimized] [--frames clip|fd]
+                               [--target-bytes N [--quality-range lo:hi]]
 """
 import ctypes
 
@@ -21,6 +27,8 @@ def main():
     ap.add_argument("--no-copy-rate", action="store_true")
     ap.add_argument("--huffman", choices=("fixed", "optimized"), default="fixed")
     ap.add_argument("--frames", choices=("clip", "fd"), default="clip")
+    ap.add_argument("--target-bytes", type=int, default=None)
+    ap.add_argument("--quality-range", default="10:95")
     a = ap.parse_args()
 
     import numpy as np
@@ -43,21 +51,41 @@ def main():
     opt = a.huffman == "optimized"
     bound = ctypes.c_size_t()
     N.check(L.dvc_jpeg_bound(W, H, N.FMT_BGR, ctypes.byref(bound)))
-    stride = (bound.value + (N.JPEG_OPT_PREFIX_MAX if opt else 0) + 255) & ~255
+    rate = a.target_bytes is not None
+    stride = (bound.value + (N.JPEG_RATE_PREFIX_MAX if rate else N.JPEG_OPT_PREFIX_MAX if opt else 0) + 255) & ~255
     out = torch.empty((B, stride), dtype=torch.uint8, device="cuda")
     sizes = torch.zeros(B, dtype=torch.int32, device="cuda")
     s = torch.cuda.Stream()
     h = ctypes.c_void_p()
-    N.check(L.dvc_jpeg_create(W, H, N.FMT_BGR, a.quality, B, 0, ctypes.c_void_p(s.cuda_stream),
-                              N.DVC_FLAG_DEVICE_PTRS | (N.DVC_FLAG_JPEG_OPT_HUFFMAN if opt else 0), ctypes.byref(h)))
     hn = ctypes.c_size_t()
-    N.check(L.dvc_jpeg_header(h, None, 0, ctypes.byref(hn)))
+    flags = N.DVC_FLAG_DEVICE_PTRS | (N.DVC_FLAG_JPEG_OPT_HUFFMAN if opt else 0)
 
     def call():
         N.check(L.dvc_jpeg_encode(h, frames.data_ptr(), 3 * W, 3 * W * H, B, out.data_ptr(), stride, sizes.data_ptr()))
 
+    target, q_lo, q_hi = a.target_bytes, *(int(v) for v in a.quality_range.split(":"))
+    if rate and not target:   # the same frames at --quality, fixed tables: header + data
+        N.check(L.dvc_jpeg_create(W, H, N.FMT_BGR, a.quality, B, 0, ctypes.c_void_p(s.cuda_stream), N.DVC_FLAG_DEVICE_PTRS,
+                                  ctypes.byref(h)))
+        N.check(L.dvc_jpeg_header(h, None, 0, ctypes.byref(hn)))
+        call()
+        N.check(L.dvc_jpeg_sync(h))
+        L.dvc_jpeg_destroy(h)
+        target = int(sizes.cpu().numpy().astype(np.int64).sum()) // B + hn.value
+    if rate:
+        N.check(L.dvc_jpeg_create_rate(W, H, N.FMT_BGR, target, q_lo, q_hi, B, 0, ctypes.c_void_p(s.cuda_stream), flags,
+                                       ctypes.byref(h)))
+    else:
+        N.check(L.dvc_jpeg_create(W, H, N.FMT_BGR, a.quality, B, 0, ctypes.c_void_p(s.cuda_stream), flags, ctypes.byref(h)))
+    N.check(L.dvc_jpeg_header(h, None, 0, ctypes.byref(hn)))
+
     ms = time_calls(s, call, a.warmup, a.runs, a.steps)
     N.check(L.dvc_jpeg_sync(h))
+    stats = None
+    if rate:
+        buf = (ctypes.c_uint64 * len(N.JPEG_RATE_STATS))()
+        N.check(L.dvc_jpeg_rate_stats(h, buf))
+        stats = dict(zip(N.JPEG_RATE_STATS, (int(v) for v in buf)))
     L.dvc_jpeg_destroy(h)
     out_bytes = int(sizes.cpu().numpy().astype(np.int64).sum())
     best = float(np.median(ms))
@@ -80,11 +108,21 @@ def main():
         "algorithmic_GBps": round((3 * px + out_bytes) / best / 1e6, 1),
         "pipeline_GBps": round(pipeline / best / 1e6, 1),
     }
+    if rate:
+        res["metric"] = "Motion-JPEG encode at a rate target, device-resident BGR -> entropy data (dvc_jpeg_encode)"
+        res["config"].update(quality=None, target_bytes=target, quality_range=[q_lo, q_hi])
+        res["rate"] = dict(stats, rounds=1 + (q_hi - q_lo).bit_length(),
+                           mean_quality=round(stats["quality_frames"] / max(stats["frames"], 1), 2),
+                           est_bytes_per_frame=round(stats["est_bytes"] / max(stats["frames"], 1)),
+                           written_bytes_per_frame=res["total_bytes_per_frame"],
+                           written_over_target=round(res["total_bytes_per_frame"] / target, 4))
     if not a.no_copy_rate:
         res["copy_rate_GBps"] = round(N.copy_rate(0), 1)
         res["pipeline_frac_of_copy_rate"] = round(res["pipeline_GBps"] / res["copy_rate_GBps"], 4)
     if a.kernels:
-        res["kernels"] = kernel_times(__file__, "k_jpeg_", child_args(a, "--no-copy-rate", "--huffman", a.huffman, "--frames", a.frames))
+        res["kernels"] = kernel_times(__file__, "k_jpeg_", child_args(a, "--no-copy-rate", "--huffman", a.huffman, "--frames", a.frames,
+                                                                    *(["--target-bytes", str(target), "--quality-range",
+                                                                       a.quality_range] if rate else [])))
     emit(res, a.out)
 
 
