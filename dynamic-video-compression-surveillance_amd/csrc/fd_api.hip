@@ -22,37 +22,31 @@
 #include "fd_kernels.h"
 #include "klaunch.h"
 #include "host_common.h"
+#include "fd_sched.h"
 #include "yuv_kernels.h"
 #include "tune.h"
 
 using dvc_host::fail;
 using dvc_host::dct_matrix;
 using dvc_host::gauss_taps;
+using dvc_sched::NSLOT;
+using dvc_sched::GRAPH_OWN_CCL_FRAMES;
 
 // One batch's launch sequence as a HIP graph (enqueue_batch's graph path, VERDICT
 // r5 #4): the launches of the four stages as dvc::klaunch recorded them, one
-// chain in stage order, with event nodes for the recurrences across batches
-// (wait for the previous batch's stage, record this batch's). A later batch of
-// the same launch shape re-uses it with the arguments that changed set in place.
+// chain in stage order, with the event nodes of the batch's plan (fd_sched.h).
+// A later batch of the same launch shape re-uses it with the arguments and the
+// waited-for events that changed set in place.
 struct FdGraph {
     std::vector<dvc::KNode> rec[4];          // front, contour filter, accumulate, output: arguments as set in ge
     std::vector<hipGraphNode_t> node[4];
+    std::vector<std::pair<hipGraphNode_t, hipEvent_t>> wait[4];   // the plan's waits: node, the event it waits for now
+    bool records[4] = {};                    // the stage records its event
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     uint64_t used = 0;                       // seq of its last launch (least recently used is replaced)
-    bool shared = false;                     // its contour filter runs on the shared working set:
-    hipGraphNode_t wait_ccl = nullptr;       //   the wait for the set's previous user (event set per launch)
-    hipEvent_t wait_ev = nullptr;            //   the event that node waits for now
 };
 constexpr int NGRAPH = 4;                    // graphs kept per slot (launch shapes: frame count, outputs, format)
-#ifndef DVC_GRAPH_OWN_CCL_FRAMES
-#define DVC_GRAPH_OWN_CCL_FRAMES 128
-#endif
-// graph batches up to this many frames run their contour filter on the slot's
-// own working set (Slot::gc: consecutive batches' filters overlap; four sets of
-// up to 128 1080p frames are ~9 GB); longer ones on the shared set the stage
-// streams use, after its previous user's filter
-constexpr int GRAPH_OWN_CCL_FRAMES = DVC_GRAPH_OWN_CCL_FRAMES;
 
 // Buffers of one batch in flight (max_batch frames): motion masks, contour-
 // filter scratch, kept masks, the dilate -> accumulate -> out bits, and the
@@ -64,14 +58,7 @@ struct Slot {
     uint64_t *dbits = nullptr, *rbits = nullptr, *zbits = nullptr;  // generic back end (row-major planes)
     uint8_t* fin = nullptr;    // resized / re-pitched / converted input frames (pitch ip), allocated when needed
     uint8_t* fsrc = nullptr;   // YUV frames converted to BGR at the source size, before the resize (pitch sip)
-    hipEvent_t ev_front = nullptr, ev_ccl = nullptr, ev_acc = nullptr, ev_out = nullptr;
-    bool recorded = false;  // the events hold a batch that the next user of the slot must wait for
-    // the output bytes its batch writes ([lo, hi) of overlay and compressed; empty
-    // when not requested): a fused front writes outputs before the previous
-    // batches' k_fix4 have run, so it waits for those that write the same bytes
-    uintptr_t olo[2] = {0, 0}, ohi[2] = {0, 0};
-    bool graph = false;     // its last batch ran as a graph: ev_front, ev_acc, ev_out were recorded,
-    bool shared_ccl = false;  // and ev_ccl when its contour filter ran on the shared working set
+    hipEvent_t ev[dvc_sched::NSTG] = {};   // recorded after each stage of its batch (fd_sched.h: which, and who waits)
     std::vector<FdGraph> graphs;   // the graph path's graphs of this slot's batches
     // the graph path's contour filter: the slot's own working set (S.c's
     // mbits / kbits / kocc with its own run index, parents and areas), so
@@ -81,11 +68,6 @@ struct Slot {
     dvc_host::DevMem gc_mem;
     int gc_frames = 0;      // frames gc holds
 };
-
-// Batches in flight: four slots (the graph path launches each slot's batches
-// on its own stream, so up to four short batches overlap; the stage streams
-// keep the four stages of four batches in flight).
-constexpr int NSLOT = 4;
 
 // Host-pointer path: two staging sets, so chunk c+1's frames go up while chunk
 // c computes and chunk c-1's outputs come down.
@@ -135,7 +117,8 @@ struct dvc_fd {
     int max_batch = 1;
     int SW = 0;          // 64-block words per block row
     size_t sstride = 0;  // static-block bit words per frame
-    uint64_t frames = 0, seq = 0;  // frames stepped, batches launched
+    uint64_t frames = 0;           // frames stepped
+    dvc_sched::State sched;        // what the ordering plan of the next batch depends on (fd_sched.h)
     int last_n = 0;                // frames of the last batch
     Slot slot[NSLOT];
     Stage stage[NSTAGE];
@@ -157,7 +140,6 @@ struct dvc_fd {
     size_t ev_used = 0;
     bool last_fused = false;   // the last batch ran the fused front (KTIMING timed k_front, not k_out)
     bool graph_ok = true;      // short device-frame batches take the graph path (DVC_FD_GRAPH=0 at create: never)
-    bool prev_graph = false;   // the last batch ran as a graph (its stages ran on its slot's graph stream)
     uint64_t graph_batches = 0, graph_builds = 0;   // batches launched as graphs, graphs built (dvc_fd_graph_stats)
 
     ~dvc_fd()
@@ -180,15 +162,21 @@ struct dvc_fd {
     {
         return has_user ? dvc_host::fork_streams(user, ev_user, {stream, s_front, s_acc, s_out}) : hipSuccess;
     }
+    // The stream a stage runs on (stage streams), and the one a slot's graphs are launched on
+    hipStream_t stage_stream(int stage) const
+    {
+        return stage == dvc_sched::FRONT ? s_front : stage == dvc_sched::FILTER ? stream
+             : stage == dvc_sched::ACCUM ? s_acc : s_out;
+    }
+    hipStream_t graph_stream(int slot) const { return stage_stream(dvc_sched::slot_stream(slot)); }
+    // `s` waits for the plan's events
+    hipError_t wait(hipStream_t s, const dvc_sched::Waits& w) const
+    {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < w.n && e == hipSuccess; ++i) e = hipStreamWaitEvent(s, slot[w.e[i].slot].ev[w.e[i].stage], 0);
+        return e;
+    }
 };
-
-// The stream a slot's graphs are launched on: one of the handle's four streams
-// per slot (each its own hardware queue at the default 4), so consecutive
-// batches' graphs overlap — batch i's contour filter beside batch i+1's front
-static hipStream_t graph_stream(dvc_fd* h, int k)
-{
-    return k == 0 ? h->stream : k == 1 ? h->s_acc : k == 2 ? h->s_out : h->s_front;
-}
 
 // Internal streams -> the caller's stream: work the caller queues after this
 // call sees its outputs (overlay/compressed on s_out, acc_out on s_acc).
@@ -463,8 +451,8 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
             for (uint64_t** q : {&s.dbits, &s.rbits, &s.zbits})
                 if ((e = h->mem.alloc(q, 8 * H * WW * (size_t)mb)) != hipSuccess) return bad(e, "hipMalloc");
         }
-        for (hipEvent_t* ev : {&s.ev_front, &s.ev_ccl, &s.ev_acc, &s.ev_out})
-            if ((e = h->mem.event(ev)) != hipSuccess) return bad(e, "hipEventCreate");
+        for (hipEvent_t& ev : s.ev)
+            if ((e = h->mem.event(&ev)) != hipSuccess) return bad(e, "hipEventCreate");
     }
     // staged input frames: always needed to resize or when rows are not whole quads
     if (h->resize || p.width % 4 || h->fmt != DVC_FMT_BGR) {
@@ -541,8 +529,8 @@ int dvc_fd_create(const dvc_fd_params* prm, int device, void* hip_stream, dvc_fd
 }  // extern "C"
 
 // Frames the kernels read: the caller's in place, or staged into slot S's
-// buffer on s_front (re-pitched, or resized — cv2.resize, fd:74,91). The
-// staged buffer is rewritten only after the slot's previous batch is out.
+// buffer on s_front (re-pitched, or resized — cv2.resize, fd:74,91), behind
+// the batch's plan's waits (the slot's previous batch is out).
 // `sf` (nullable: the prime's single frame is always staged as BGR) receives
 // how the kernels read the frames: BGR, or the 4:2:0 surfaces in place.
 static int stage_input(dvc_fd* h, Slot& S, const uint8_t* src, size_t pitch, size_t fstride, int n,
@@ -565,7 +553,6 @@ static int stage_input(dvc_fd* h, Slot& S, const uint8_t* src, size_t pitch, siz
         return DVC_OK;
     }
     if (!S.fin) HIP_OK(alloc_fin(h));
-    if (S.recorded) HIP_OK(hipStreamWaitEvent(h->s_front, S.ev_out, 0));
     const size_t H = h->g.H, fs = (size_t)h->ip * H;
     if (h->fmt != DVC_FMT_BGR) {
         // the decoder's 4:2:0 surfaces -> BGR (cvtColor, what VideoCapture.read()
@@ -598,10 +585,11 @@ static int start_run(dvc_fd* h)
     HIP_OK(hipMemsetAsync(h->stats, 0, 8 * 4 * 64, h->s_front));
     HIP_OK(hipMemsetAsync(h->err, 0xff, 8, h->s_front));
     HIP_OK(hipStreamSynchronize(h->s_front));
-    h->frames = h->seq = h->err_frame = 0;
+    h->frames = h->err_frame = 0;
+    h->sched = dvc_sched::State{};   // (its caller has synced every stream)
     h->last_n = 0;
     h->primed = true;
-    h->failed = h->prev_graph = false;
+    h->failed = false;
     return DVC_OK;
 }
 
@@ -619,7 +607,7 @@ int dvc_fd_prime(dvc_fd* h, const uint8_t* bgr, size_t pitch)
     }
     HIP_OK(h->sync());  // no batch of a previous run may still be in flight
     HIP_OK(h->wait_user());
-    for (Slot& s : h->slot) s.recorded = false;
+    for (dvc_sched::SlotState& s : h->sched.slot) s.recorded = false;
     for (Stage& s : h->stage) s.busy = false;
     const uint8_t* src = bgr;
     size_t sp = pitch;
@@ -655,7 +643,7 @@ int dvc_fd_set_state(dvc_fd* h, const uint8_t* prev_gray, const uint8_t* acc)
     const size_t W = h->p.width, H = h->p.height;
     HIP_OK(h->sync());  // no batch of a previous run may still be in flight
     HIP_OK(h->wait_user());
-    for (Slot& s : h->slot) s.recorded = false;
+    for (dvc_sched::SlotState& s : h->sched.slot) s.recorded = false;
     for (Stage& s : h->stage) s.busy = false;
     HIP_OK(hipMemcpy2DAsync(h->gray[h->gcur], h->gs, prev_gray, W, W, H, hipMemcpyHostToDevice, h->s_front));
     // the acc rows have pitch AP; the padding of partial blocks stays 0 (create)
@@ -665,34 +653,21 @@ int dvc_fd_set_state(dvc_fd* h, const uint8_t* prev_gray, const uint8_t* acc)
 
 }  // extern "C"
 
-// The graph path of one batch (device frames read in place, no KTIMING): the
-// four stages' launches are recorded (dvc::klaunch),
-// matched against this slot's graphs by launch shape and launched as one
-// graph on the slot's graph stream. A call then costs one graph launch and a
-// few argument updates instead of nine launches and eleven event operations
-// across four streams (~80 us of host time a call, profiles/r6_fd_per_call_*).
-// Chain: [wait P.front] front [rec S.front] contour filter, dilate [wait P.acc]
-// accumulate [rec S.acc] outputs [rec S.out], P = the previous batch's slot —
-// the recurrences the stage streams give the direct path (previous gray,
-// accumulated mask). A short batch's contour filter runs on the slot's own
-// working set (graph_ccl) and needs no order across batches; a longer one's on
-// the shared set, between [wait for the set's previous user] and [rec S.ccl].
-// Before the launch, on the graph stream: the slot's
-// previous batch (S.out: every buffer of the slot is free) and `wait_out`
-// (earlier batches whose outputs the fused front overwrites).
 // The slot's own contour-filter working set for short graph batches (Slot::gc):
 // ~17 MB a 1080p frame, grown to the batch (powers of two up to
 // min(max_batch, GRAPH_OWN_CCL_FRAMES) frames), so per-frame calls hold four
 // one-frame sets. A graph keeps the old pointers until its next launch sets
 // the changed arguments.
-static int graph_ccl(dvc_fd* h, Slot& S, int n)
+static int graph_ccl(dvc_fd* h, int k, int n)
 {
+    Slot& S = h->slot[k];
     if (n <= S.gc_frames) return DVC_OK;
     int cap = 1;
     while (cap < n) cap *= 2;
     cap = std::min(cap, std::min(h->max_batch, GRAPH_OWN_CCL_FRAMES));
     if (!S.gc_mem.dev.empty()) {
-        if (S.recorded) HIP_OK(hipEventSynchronize(S.ev_out));   // the slot's last batch is done with the set
+        // the slot's last batch is done with the set
+        if (h->sched.slot[k].recorded) HIP_OK(hipEventSynchronize(S.ev[dvc_sched::OUTPUT]));
         S.gc_mem.free_all();
         S.gc_frames = 0;
     }
@@ -710,26 +685,42 @@ static int graph_ccl(dvc_fd* h, Slot& S, int n)
         }
     }
     // every frame slice's OUTSIDE gap node is its own root before any k_band (as at create)
-    HIP_OK(hipMemsetAsync(S.gc.gpar, 0, sz[dvc::CclBufs::I_GPAR], graph_stream(h, (int)(&S - h->slot))));
+    HIP_OK(hipMemsetAsync(S.gc.gpar, 0, sz[dvc::CclBufs::I_GPAR], h->graph_stream(k)));
     S.gc_frames = cap;
     return DVC_OK;
 }
 
-static int enqueue_graph(dvc_fd* h, Slot& S, std::vector<dvc::KNode> (&rec)[4], const std::vector<hipEvent_t>& wait_out,
-                         bool shared)
+static hipKernelNodeParams node_params(const dvc::KNode& kn, std::vector<void*>& pp)
 {
-    const int k = (int)(h->seq % NSLOT);
-    Slot& P = h->slot[(h->seq + NSLOT - 1) % NSLOT];
-    hipStream_t z = graph_stream(h, k);
-    // the shared working set's previous user is done with it: the previous
-    // batch's filter when it ran there (ev_ccl), else its accumulate (ev_acc,
-    // which follows every earlier batch's accumulate, each after its filter)
-    const hipEvent_t ccl_ev = P.recorded && P.graph && !P.shared_ccl ? P.ev_acc : P.ev_ccl;
+    hipKernelNodeParams kp{};
+    kp.func = const_cast<void*>(kn.f);
+    kp.gridDim = kn.grid;
+    kp.blockDim = kn.block;
+    kp.sharedMemBytes = kn.shm;
+    kn.params(pp);
+    kp.kernelParams = pp.data();
+    return kp;
+}
+
+// The graph path of one batch (device frames read in place, no KTIMING): the
+// four stages' launches as recorded (dvc::klaunch) are matched against this
+// slot's graphs by launch shape and launched as one graph on the slot's graph
+// stream. A call then costs one graph launch and a few argument updates
+// instead of nine launches and eleven event operations across four streams
+// (~80 us of host time a call, profiles/r6_fd_per_call_*). The chain's wait
+// and record nodes and the waits before the launch are the plan's (fd_sched.h).
+static int enqueue_graph(dvc_fd* h, int k, std::vector<dvc::KNode> (&rec)[4], const dvc_sched::Plan& pl)
+{
+    Slot& S = h->slot[k];
+    const bool recorded = h->sched.slot[k].recorded;
+    const hipEvent_t ev_out = S.ev[dvc_sched::OUTPUT];
+    auto event = [&](dvc_sched::Ev e) { return h->slot[e.slot].ev[e.stage]; };
     FdGraph* G = nullptr;
     for (FdGraph& x : S.graphs) {
-        bool same = x.shared == shared;
+        bool same = true;
         for (int sg = 0; sg < 4 && same; ++sg) {
-            same = x.rec[sg].size() == rec[sg].size();
+            same = x.rec[sg].size() == rec[sg].size() && (int)x.wait[sg].size() == pl.stage[sg].n &&
+                   x.records[sg] == pl.record[sg];
             for (size_t u = 0; same && u < rec[sg].size(); ++u) same = x.rec[sg][u].same_shape(rec[sg][u]);
         }
         if (same) {
@@ -739,34 +730,31 @@ static int enqueue_graph(dvc_fd* h, Slot& S, std::vector<dvc::KNode> (&rec)[4], 
     }
     std::vector<void*> pp;
     if (G) {
-        // the exec's previous launch (batch i-3, this slot's) must have read its
+        // the exec's previous launch (batch i-4, this slot's) must have read its
         // arguments before they are overwritten: wait for it on the host (it is
-        // three batches back, so the device keeps two batches queued meanwhile)
-        if (S.recorded) HIP_OK(hipEventSynchronize(S.ev_out));
-        for (int sg = 0; sg < 4; ++sg)
+        // four batches back, so the device keeps three batches queued meanwhile)
+        if (recorded) HIP_OK(hipEventSynchronize(ev_out));
+        for (int sg = 0; sg < 4; ++sg) {
             for (size_t u = 0; u < rec[sg].size(); ++u) {
                 dvc::KNode& cur = G->rec[sg][u];
                 if (cur.args == rec[sg][u].args) continue;
                 cur.args.swap(rec[sg][u].args);
-                hipKernelNodeParams kp{};
-                kp.func = const_cast<void*>(cur.f);
-                kp.gridDim = cur.grid;
-                kp.blockDim = cur.block;
-                kp.sharedMemBytes = cur.shm;
-                cur.params(pp);
-                kp.kernelParams = pp.data();
+                const hipKernelNodeParams kp = node_params(cur, pp);
                 HIP_OK(hipGraphExecKernelNodeSetParams(G->ge, G->node[sg][u], &kp));
             }
-        if (shared && G->wait_ev != ccl_ev) {
-            HIP_OK(hipGraphExecEventWaitNodeSetEvent(G->ge, G->wait_ccl, ccl_ev));
-            G->wait_ev = ccl_ev;
+            for (int u = 0; u < pl.stage[sg].n; ++u) {   // the waits whose event differs from the one the node holds
+                const hipEvent_t e = event(pl.stage[sg].e[u]);
+                if (G->wait[sg][u].second == e) continue;
+                HIP_OK(hipGraphExecEventWaitNodeSetEvent(G->ge, G->wait[sg][u].first, e));
+                G->wait[sg][u].second = e;
+            }
         }
     } else {
         if ((int)S.graphs.size() >= NGRAPH) {   // replace the least recently used one
             size_t lru = 0;
             for (size_t u = 1; u < S.graphs.size(); ++u)
                 if (S.graphs[u].used < S.graphs[lru].used) lru = u;
-            if (S.recorded) HIP_OK(hipEventSynchronize(S.ev_out));
+            if (recorded) HIP_OK(hipEventSynchronize(ev_out));
             (void)hipGraphExecDestroy(S.graphs[lru].ge);
             (void)hipGraphDestroy(S.graphs[lru].g);
             S.graphs.erase(S.graphs.begin() + (long)lru);
@@ -785,47 +773,30 @@ static int enqueue_graph(dvc_fd* h, Slot& S, std::vector<dvc::KNode> (&rec)[4], 
         } drop{NG};
         G = &NG;
         HIP_OK(hipGraphCreate(&G->g, 0));
-        // (short batches: no wait for the previous batch's contour filter, the
-        // slot has its own working set, and no record of this one's — an event
-        // node costs ~5 us of the chain's latency on the device)
-        G->shared = shared;
-        const hipEvent_t waits[4] = {P.ev_front, shared ? ccl_ev : nullptr, P.ev_acc, nullptr};
-        const hipEvent_t recs[4] = {S.ev_front, shared ? S.ev_ccl : nullptr, S.ev_acc, S.ev_out};
         hipGraphNode_t last = nullptr;   // one chain: every node depends on the one before
         auto dep = [&]() { return last ? 1u : 0u; };
         for (int sg = 0; sg < 4; ++sg) {
             hipGraphNode_t nd = nullptr;
-            // the accumulate stage waits for the previous batch's accumulate only
-            // before its last kernel (k_acc: the accumulated mask); k_dilate, when
-            // the stage has it, reads this batch's kept mask alone. (The graph is
-            // one chain, so k_paint_dilate in the filter stage is behind the
-            // wait for the shared set and before the record of ev_ccl, and the
-            // slot's dblk / docc are free since S.ev_out, waited for at launch.)
-            const size_t wat = sg == 2 && !rec[sg].empty() ? rec[sg].size() - 1 : 0;
+            // the accumulate stage's waits stand before its last kernel only (k_acc:
+            // the accumulated mask); k_dilate, when the stage has it, reads this
+            // batch's kept mask alone
+            const size_t wat = sg == dvc_sched::ACCUM && !rec[sg].empty() ? rec[sg].size() - 1 : 0;
             for (size_t u = 0; u <= rec[sg].size(); ++u) {
-                if (u == wat && waits[sg]) {
-                    HIP_OK(hipGraphAddEventWaitNode(&nd, G->g, last ? &last : nullptr, dep(), waits[sg]));
-                    if (sg == 1) {
-                        G->wait_ccl = nd;
-                        G->wait_ev = waits[sg];
-                    }
+                for (int w = 0; u == wat && w < pl.stage[sg].n; ++w) {
+                    const hipEvent_t e = event(pl.stage[sg].e[w]);
+                    HIP_OK(hipGraphAddEventWaitNode(&nd, G->g, last ? &last : nullptr, dep(), e));
+                    G->wait[sg].emplace_back(nd, e);
                     last = nd;
                 }
                 if (u == rec[sg].size()) break;
-                dvc::KNode& kn = rec[sg][u];
-                hipKernelNodeParams kp{};
-                kp.func = const_cast<void*>(kn.f);
-                kp.gridDim = kn.grid;
-                kp.blockDim = kn.block;
-                kp.sharedMemBytes = kn.shm;
-                kn.params(pp);
-                kp.kernelParams = pp.data();
+                const hipKernelNodeParams kp = node_params(rec[sg][u], pp);
                 HIP_OK(hipGraphAddKernelNode(&nd, G->g, last ? &last : nullptr, dep(), &kp));
                 G->node[sg].push_back(nd);
                 last = nd;
             }
-            if (recs[sg]) {
-                HIP_OK(hipGraphAddEventRecordNode(&nd, G->g, last ? &last : nullptr, dep(), recs[sg]));
+            G->records[sg] = pl.record[sg];
+            if (pl.record[sg]) {
+                HIP_OK(hipGraphAddEventRecordNode(&nd, G->g, last ? &last : nullptr, dep(), S.ev[sg]));
                 last = nd;
             }
             G->rec[sg].swap(rec[sg]);
@@ -836,39 +807,28 @@ static int enqueue_graph(dvc_fd* h, Slot& S, std::vector<dvc::KNode> (&rec)[4], 
         G = &S.graphs.back();
         h->graph_builds++;
     }
-    if (S.recorded) HIP_OK(hipStreamWaitEvent(z, S.ev_out, 0));
-    for (hipEvent_t e : wait_out) HIP_OK(hipStreamWaitEvent(z, e, 0));
-    HIP_OK(hipGraphLaunch(G->ge, z));
-    G->used = h->seq;
+    HIP_OK(h->wait(h->graph_stream(k), pl.pre));
+    HIP_OK(hipGraphLaunch(G->ge, h->graph_stream(k)));
+    G->used = h->sched.seq;
     h->graph_batches++;
     return DVC_OK;
 }
 
-// Enqueue one batch i of n <= max_batch frames, slot S = i % NSLOT (j = i - NSLOT
-// = the slot's previous batch):
-//   s_front:         [wait ccl(j) (+ out(j) when staging or fused; fused: also
-//                    out(i-1) .. out(j+1) where their output bytes overlap)]
-//                    stage, front(i) (fused: + speculative outputs) -> ev_front   (S.mbits free)
-//   stream:          [wait ev_front, acc(j)]  contour filter(i) -> ev_ccl (S.kbits free)
-//   s_acc:           [wait ev_ccl, out(j)]    dilate + accumulate(i) -> ev_acc (S bits free)
-//   s_out:           [wait ev_acc]            k_out(i), or k_out_gen + k_fix4(i) when fused -> ev_out
-// so front(i+2), the contour filter of i+1, the accumulation of i and the
-// output of i-1 can all be in flight; the two recurrences (previous gray,
-// accumulated mask) are serial, each on its own stream. Batches of device
-// frames read in place take the graph path instead (enqueue_graph): the same
-// kernels, arguments and dependencies.
+// Enqueue one batch of n <= max_batch frames in slot seq % NSLOT: four stages
+// (front, contour filter, dilate + accumulate, outputs) on the four stage
+// streams or, for device frames read in place, as one graph (enqueue_graph) —
+// the same kernels and arguments either way. Which path, and which events each
+// stage waits for and records, is dvc_sched::plan (fd_sched.h, with the buffers
+// each stage touches); this function executes the plan.
 // With the kept mask on chip (fuse_paint_dilate) the filter stage ends in
-// k_paint_dilate and the accumulate stage is k_acc alone. The events stay as
-// they are: ev_ccl, recorded after k_paint_dilate, still frees S.mbits and the
-// shared filter set (its last reads of rs, re, fpar, gE and area2 are that
-// kernel's, as they were k_paint's), and the filter stage's wait for acc(j)
-// now also keeps k_paint_dilate's dblk / docc stores behind k_acc(j), their
-// only reader.
+// k_paint_dilate and the accumulate stage is k_acc alone; the events stay as
+// they are (the filter's is recorded after k_paint_dilate, whose reads of the
+// filter set are the batch's last, as they were k_paint's).
 static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fstride, int n, uint8_t* ov, uint8_t* cp,
                          size_t ostride, int crows)
 {
-    Slot& S = h->slot[h->seq % NSLOT];
-    hipStream_t s_ccl = h->stream;
+    const int k = (int)(h->sched.seq % NSLOT);
+    Slot& S = h->slot[k];
 #ifdef DVC_ABLATION
     // DVC_FD_SKIP (stage ablation for profiling only, results are wrong when
     // set): bit 0 front, 1 contour filter, 2 dilate + accumulate, 3 output.
@@ -884,53 +844,7 @@ static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fst
     constexpr int skip = 0;
 #endif
     const bool timed = h->p.flags & DVC_FLAG_KTIMING;
-    // the byte ranges this batch's outputs cover (frames of ostride, the last
-    // one ofb bytes), and the batches in flight whose outputs overlap them
-    uintptr_t olo[2], ohi[2];
-    {
-        const size_t span = n > 0 ? (size_t)(n - 1) * ostride + h->ofb : 0;
-        olo[0] = (uintptr_t)ov;
-        ohi[0] = ov ? (uintptr_t)ov + span : 0;
-        olo[1] = (uintptr_t)cp;
-        ohi[1] = cp ? (uintptr_t)cp + span : 0;
-    }
-    std::vector<hipEvent_t> overlapping;
-    for (int k = 1; k < NSLOT; ++k) {
-        const Slot& P = h->slot[(h->seq + NSLOT - k) % NSLOT];
-        if (!P.recorded) continue;
-        bool overlap = false;
-        for (int u = 0; u < 2; ++u)
-            for (int v = 0; v < 2; ++v)
-                overlap = overlap ||
-                          (ohi[u] > olo[u] && P.ohi[v] > P.olo[v] && olo[u] < P.ohi[v] && P.olo[v] < ohi[u]);
-        if (overlap) overlapping.push_back(P.ev_out);
-    }
-    // the graph path: device frames the kernels read in place (no staging
-    // launches); DVC_FD_GRAPH=0 at create turns it off. Not for a long batch
-    // whose outputs overlap a batch in flight (one output set re-used): its
-    // front then waits for that batch's whole chain, a path the stage streams
-    // run ~3 % faster (experiments/README.md round 6)
-    const bool graph = h->graph_ok && (h->p.flags & DVC_FLAG_DEVICE_PTRS) && !timed && !skip &&
-                       (n <= GRAPH_OWN_CCL_FRAMES || overlapping.empty()) &&
-                       in_place(h, src, pitch, fstride, n) != 0;
-    if (!graph && h->prev_graph) {
-        // the previous batch ran on its slot's graph stream: the stage streams
-        // take its recurrences from its events
-        const Slot& P = h->slot[(h->seq + NSLOT - 1) % NSLOT];
-        HIP_OK(hipStreamWaitEvent(h->s_front, P.ev_front, 0));
-        // (a short graph batch records no ev_ccl: its ev_acc follows every
-        // earlier batch's filter on the shared working set)
-        HIP_OK(hipStreamWaitEvent(s_ccl, P.shared_ccl ? P.ev_ccl : P.ev_acc, 0));
-        HIP_OK(hipStreamWaitEvent(h->s_acc, P.ev_acc, 0));
-        HIP_OK(hipStreamWaitEvent(h->s_out, P.ev_out, 0));
-    }
-    if (S.recorded && !graph) HIP_OK(hipStreamWaitEvent(h->s_front, S.graph ? S.ev_out : S.ev_ccl, 0));
-    const uint8_t* d = nullptr;
-    int dp = 0;
-    size_t dfs = 0;
-    dvc::SrcFmt sf{};
-    int rc = stage_input(h, S, src, pitch, fstride, n, &d, &dp, &dfs, crows, &sf);
-    if (rc) return rc;
+    const int direct = in_place(h, src, pitch, fstride, n);   // 0: staged, 2: read as 4:2:0 surfaces
     const int opitch = 3 * h->p.width;
     const int obytes = (opitch % 4) || (ostride % 4) || ((uintptr_t)ov & 3) || ((uintptr_t)cp & 3);
     const bool out_i420 = h->p.flags & DVC_FLAG_OUT_I420;
@@ -945,23 +859,30 @@ static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fst
     // the VALU-bound front the period — 268-270 k against 288 k Mpx/s for the
     // one-pass k_out<8> at the __main__ kwargs, experiments/README.md)
     const bool fused = fuse_env && !(h->p.flags & DVC_FLAG_FD_UNFUSED) && !obytes && (ov || cp) &&
-                       ((h->B == 4 && h->SW <= 64) ||
-                        (h->B == 8 && h->fused8 && sf.fmt == DVC_FMT_BGR && !out_i420));
-    for (int u = 0; u < 2; ++u) {
-        S.olo[u] = olo[u];
-        S.ohi[u] = ohi[u];
+                       ((h->B == 4 && h->SW <= 64) || (h->B == 8 && h->fused8 && direct != 2 && !out_i420));
+    dvc_sched::Request rq;
+    rq.n = n;
+    {   // the byte ranges this batch's outputs cover (frames of ostride, the last one ofb bytes)
+        const size_t span = n > 0 ? (size_t)(n - 1) * ostride + h->ofb : 0;
+        rq.olo[0] = (uintptr_t)ov;
+        rq.ohi[0] = ov ? (uintptr_t)ov + span : 0;
+        rq.olo[1] = (uintptr_t)cp;
+        rq.ohi[1] = cp ? (uintptr_t)cp + span : 0;
     }
+    rq.staged = direct == 0;
+    // (DVC_FD_GRAPH=0 at create turns the graph path off)
+    rq.graph_ok = h->graph_ok && (h->p.flags & DVC_FLAG_DEVICE_PTRS) && !timed && !skip;
+    rq.fused = fused;
+    const dvc_sched::Plan pl = dvc_sched::plan(h->sched, rq);
+    if (!pl.graph) HIP_OK(h->wait(h->s_front, pl.pre));
+    const uint8_t* d = nullptr;
+    int dp = 0;
+    size_t dfs = 0;
+    dvc::SrcFmt sf{};
+    int rc = stage_input(h, S, src, pitch, fstride, n, &d, &dp, &dfs, crows, &sf);
+    if (rc) return rc;
     dvc::FrontOut fo{};
-    std::vector<hipEvent_t> wait_out;   // fused: earlier batches whose outputs this one's front overwrites
     if (fused) {
-        // the speculative stores must not land before an earlier batch's k_fix4
-        // rewrites the same bytes: wait for the slot's previous batch (so every
-        // k_fix4 up to batch i-3 is done, s_out being in order) and for batches
-        // i-1, i-2 where their outputs overlap this one's
-        if (S.recorded && !graph) HIP_OK(hipStreamWaitEvent(h->s_front, S.ev_out, 0));
-        wait_out.swap(overlapping);
-        if (!graph)
-            for (hipEvent_t e : wait_out) HIP_OK(hipStreamWaitEvent(h->s_front, e, 0));
         fo.ov = ov;
         fo.cp = cp;
         fo.opitch = opitch;
@@ -1023,73 +944,55 @@ static int enqueue_batch(dvc_fd* h, const uint8_t* src, size_t pitch, size_t fst
     // which writes the slot's dblk / docc, and the accumulate stage is k_acc
     // alone (DVC_FLAG_FD_KEPT_PLANE: k_paint -> kbits -> k_dilate instead)
     const bool onchip = !(h->p.flags & DVC_FLAG_FD_KEPT_PLANE) && dvc::fuse_paint_dilate(S.c, a);
-    if (graph) {
+    if (pl.graph && !pl.shared) {
+        rc = graph_ccl(h, k, n);
+        if (rc) return rc;
+    }
+    auto launch = [&](int sg, hipStream_t z) {
+        switch (sg) {
+        case dvc_sched::FRONT:
+            return dvc::launch_front(d, dp, dfs, sf, n, h->gray[h->gcur], h->gray[h->gcur ^ 1], h->gs, S.c.mbits, h->g,
+                                     h->p.ithresh, z, fused ? &fo : nullptr);
+        case dvc_sched::FILTER:
+            return dvc::launch_ccl(pl.shared ? S.c : S.gc, h->g, n, h->p.min_area2, z, onchip ? &a : nullptr);
+        case dvc_sched::ACCUM: return dvc::launch_accumulate(a, z, onchip);
+        default: return dvc::launch_out(a, z, fused);
+        }
+    };
+    if (pl.graph) {
         std::vector<dvc::KNode> rec[4];
         hipError_t e[4];
-        hipStream_t z = graph_stream(h, (int)(h->seq % NSLOT));
-        const bool shared = n > GRAPH_OWN_CCL_FRAMES;
-        if (!shared) {
-            rc = graph_ccl(h, S, n);
-            if (rc) return rc;
+        for (int sg = 0; sg < 4; ++sg) {
+            dvc::g_krec = &rec[sg];
+            e[sg] = launch(sg, h->graph_stream(k));
         }
-        dvc::g_krec = &rec[0];
-        e[0] = dvc::launch_front(d, dp, dfs, sf, n, h->gray[h->gcur], h->gray[h->gcur ^ 1], h->gs, S.c.mbits, h->g,
-                                 h->p.ithresh, z, fused ? &fo : nullptr);
-        dvc::g_krec = &rec[1];
-        e[1] = dvc::launch_ccl(shared ? S.c : S.gc, h->g, n, h->p.min_area2, z, onchip ? &a : nullptr);
-        dvc::g_krec = &rec[2];
-        e[2] = dvc::launch_accumulate(a, z, onchip);
-        dvc::g_krec = &rec[3];
-        e[3] = dvc::launch_out(a, z, fused);
         dvc::g_krec = nullptr;
         for (hipError_t x : e) HIP_OK(x);
-        rc = enqueue_graph(h, S, rec, wait_out, shared);
+        rc = enqueue_graph(h, k, rec, pl);
         if (rc) return rc;
-        h->prev_graph = true;
-        S.graph = true;
-        S.shared_ccl = shared;
     } else {
         // KTIMING: events around the dominant HBM kernel — the fused front on
         // s_front, else k_out on s_out
-        if (timed) {
-            while (h->ev.size() < h->ev_used + 2) {
-                hipEvent_t e;
-                HIP_OK(hipEventCreate(&e));
-                h->ev.push_back(e);
+        const int tk = !timed ? -1 : fused ? dvc_sched::FRONT : dvc_sched::OUTPUT;
+        while (timed && h->ev.size() < h->ev_used + 2) {
+            hipEvent_t e;
+            HIP_OK(hipEventCreate(&e));
+            h->ev.push_back(e);
+        }
+        for (int sg = 0; sg < 4; ++sg) {
+            hipStream_t z = h->stage_stream(sg);
+            HIP_OK(h->wait(z, pl.stage[sg]));
+            if (sg == tk) HIP_OK(hipEventRecord(h->ev[h->ev_used], z));
+            if (!(skip >> sg & 1)) HIP_OK(launch(sg, z));
+            if (sg == tk) {
+                HIP_OK(hipEventRecord(h->ev[h->ev_used + 1], z));
+                h->ev_used += 2;
             }
+            if (pl.record[sg]) HIP_OK(hipEventRecord(S.ev[sg], z));
         }
-        if (timed && fused) HIP_OK(hipEventRecord(h->ev[h->ev_used], h->s_front));
-        if (!(skip & 1))
-            HIP_OK(dvc::launch_front(d, dp, dfs, sf, n, h->gray[h->gcur], h->gray[h->gcur ^ 1], h->gs, S.c.mbits, h->g,
-                                     h->p.ithresh, h->s_front, fused ? &fo : nullptr));
-        if (timed && fused) {
-            HIP_OK(hipEventRecord(h->ev[h->ev_used + 1], h->s_front));
-            h->ev_used += 2;
-        }
-        HIP_OK(hipEventRecord(S.ev_front, h->s_front));
-        HIP_OK(hipStreamWaitEvent(s_ccl, S.ev_front, 0));
-        if (S.recorded) HIP_OK(hipStreamWaitEvent(s_ccl, S.ev_acc, 0));
-        if (!(skip & 2)) HIP_OK(dvc::launch_ccl(S.c, h->g, n, h->p.min_area2, s_ccl, onchip ? &a : nullptr));
-        HIP_OK(hipEventRecord(S.ev_ccl, s_ccl));
-        HIP_OK(hipStreamWaitEvent(h->s_acc, S.ev_ccl, 0));
-        if (S.recorded) HIP_OK(hipStreamWaitEvent(h->s_acc, S.ev_out, 0));
-        if (!(skip & 4)) HIP_OK(dvc::launch_accumulate(a, h->s_acc, onchip));
-        HIP_OK(hipEventRecord(S.ev_acc, h->s_acc));
-        HIP_OK(hipStreamWaitEvent(h->s_out, S.ev_acc, 0));
-        if (timed && !fused) HIP_OK(hipEventRecord(h->ev[h->ev_used], h->s_out));
-        if (!(skip & 8)) HIP_OK(dvc::launch_out(a, h->s_out, fused));
-        if (timed && !fused) {
-            HIP_OK(hipEventRecord(h->ev[h->ev_used + 1], h->s_out));
-            h->ev_used += 2;
-        }
-        HIP_OK(hipEventRecord(S.ev_out, h->s_out));
-        h->prev_graph = false;
-        S.graph = false;
-        S.shared_ccl = true;
     }
+    dvc_sched::advance(h->sched, rq, pl);
     h->gcur ^= 1;
-    S.recorded = true;
-    h->seq++;
     h->frames += (uint64_t)n;
     h->last_n = n;
     return DVC_OK;
@@ -1133,6 +1036,7 @@ static int run_frames(dvc_fd* h, const uint8_t* bgr, size_t pitch, size_t fstrid
     HIP_OK(h->wait_user());
     const bool devp = h->p.flags & DVC_FLAG_DEVICE_PTRS;
     if (devp) {
+        const uint64_t first = h->sched.seq;
         for (int f0 = 0; f0 < n; f0 += h->max_batch) {
             const int m = std::min(h->max_batch, n - f0);
             int rc = enqueue_batch(h, bgr + (size_t)f0 * fstride, pitch, fstride, m,
@@ -1140,14 +1044,14 @@ static int run_frames(dvc_fd* h, const uint8_t* bgr, size_t pitch, size_t fstrid
                                    compressed ? compressed + (size_t)f0 * ostride : nullptr, ostride, h->crows);
             if (rc) return rc;
         }
-        if (h->prev_graph && (acc_out || h->has_user)) {
-            // the last batch ran on its slot's graph stream: the acc copy and the
-            // caller's join below follow its accumulate and output stages
-            const Slot& L = h->slot[(h->seq + NSLOT - 1) % NSLOT];
-            HIP_OK(hipStreamWaitEvent(h->s_acc, L.ev_acc, 0));
-            HIP_OK(hipStreamWaitEvent(h->s_out, L.ev_out, 0));
-        }
+        // the acc copy and the caller's join follow the call's graph batches, which
+        // ran on their slots' streams
+        const dvc_sched::Join j = dvc_sched::join(h->sched, first, acc_out != nullptr, h->has_user);
+        HIP_OK(h->wait(h->s_acc, j.acc));
+        HIP_OK(h->wait(h->s_out, j.out));
         if (acc_out) HIP_OK(hipMemcpy2DAsync(acc_out, W, h->acc, h->AP, W, H, hipMemcpyDeviceToDevice, h->s_acc));
+        if (j.record_acc)
+            HIP_OK(hipEventRecord(h->slot[(h->sched.seq - 1) % NSLOT].ev[dvc_sched::ACCUM], h->s_acc));
         HIP_OK(join_user(h));
         return DVC_OK;
     }
@@ -1269,7 +1173,7 @@ int dvc_fd_read_plane(dvc_fd* h, int plane, uint8_t* dst)
         return DVC_OK;
     }
     // the last frame of the last batch
-    const dvc::CclBufs c = h->slot[(h->seq - 1) % NSLOT].c.frame((size_t)h->last_n - 1, h->g);
+    const dvc::CclBufs c = h->slot[(h->sched.seq - 1) % NSLOT].c.frame((size_t)h->last_n - 1, h->g);
     const uint64_t* src = plane == DVC_PLANE_MOTION ? c.mbits
                         : plane == DVC_PLANE_FILTERED ? c.kbits
                         : plane == DVC_PLANE_DILATED ? h->dbg_dil : nullptr;

@@ -69,8 +69,10 @@ class FDWorker(Worker):
         :meth:`prime`/:meth:`step` are ``src_width x src_height`` (the video's,
         default the same) and are resized on the GPU (fd:74,91).
         ``max_batch``: frames one device launch covers in :meth:`step_batch`
-        (bit planes for four slots of max_batch frames in flight, the
-        contour filter's working arrays for one, fd_api.hip). ``stream``: the
+        (bit planes for four slots of max_batch frames in flight and the
+        contour filter's working arrays for one; the graph path adds a filter
+        set per slot, grown to the batch, for batches of up to 128 frames:
+        ~17 MB a 1080p frame and slot, fd_api.hip). ``stream``: the
         caller's HIP stream (``torch.cuda.Stream.cuda_stream``), joined as
         dvc_fd_create documents. ``in_format`` (kwarg) "BGR" / "I420" / "NV12":
         the frames handed over (4:2:0 decoder surfaces are converted on the GPU);

@@ -249,7 +249,7 @@ void dvc_host_free(void* p);
 
 /* Create a feed handle on `device`. The stages run on four internal streams
  * (blur/threshold front, contour filter, dilate + accumulate, overlay/compress
- * output) with three batches' buffers in flight; only the two recurrences
+ * output) with four batches' buffers in flight; only the two recurrences
  * (previous gray, accumulated mask) are serial. `hip_stream` (a hipStream_t or
  * NULL) is the caller's stream: when given, every prime/step call first waits
  * for the work queued on it before the call (e.g. the copy producing the

@@ -1,7 +1,7 @@
 """GPU parity of the FD graph path (fd_api.hip enqueue_graph).
 
 Batches of device frames read in place run as one HIP graph launch each — the
-same kernels, arguments and dependencies as the stage streams; a batch of
+same kernels and arguments as the stage streams; a batch of
 <= 128 frames runs its contour filter on its slot's own working set (grown to
 the batch), a longer one on the shared set after the set's previous user. Here: every output of a run
 whose calls switch between short and long graph batches and stream batches
@@ -9,7 +9,9 @@ whose calls switch between short and long graph batches and stream batches
 the stream-only run (DVC_FD_GRAPH=0) and the oracle;
 per-frame calls that re-use one output set (the fused front's overlap waits)
 and are read back on the caller's joined stream; the accumulated-mask copy
-of dvc_fd_step.
+of dvc_fd_step; one call split into eight graph batches read back on the
+caller's stream; unfused per-frame calls into one output set with no sync
+between them (the orderings themselves: csrc/fd_sched.h, tests/test_fd_sched.py).
 """
 import numpy as np
 import pytest
@@ -121,6 +123,74 @@ def test_graph_per_frame_one_output_set_joined_stream(gpu_lib, oracle_lib, clip9
         assert np.array_equal(h[t, 0], rov), f"overlay differs at frame {t + 1}"
         assert np.array_equal(h[t, 1], rcp), f"compressed differs at frame {t + 1}"
         assert np.array_equal(h[t, 2, :, :, 0], racc), f"acc differs at frame {t + 1}"
+    ref.close()
+
+
+def test_one_call_of_graph_batches_joined_stream(gpu_lib, oracle_lib, clip91, monkeypatch):
+    """One step_batch of 8 frames with max_batch=1 on a caller's stream: eight
+    one-frame graph batches on four streams, every one joined to the caller's
+    stream (fd_sched.h join), so the copies queued on it straight after the
+    call, with no sync, see all eight frames."""
+    import torch
+    monkeypatch.setenv("DVC_FD_GRAPH", "1")
+    dev = torch.device("cuda", 0)
+    n = 8
+    seq = torch.from_numpy(clip91[:n + 1]).to(dev)
+    user = torch.cuda.Stream(device=dev)
+    ov = torch.zeros((n, H, W, 3), dtype=torch.uint8, device=dev)
+    cp = torch.zeros_like(ov)
+    hist = torch.zeros((2, n, H, W, 3), dtype=torch.uint8, device=dev)
+    w = gpu_lib.FDWorker(W, H, device=0, device_ptrs=True, max_batch=1, stream=user.cuda_stream)
+    with torch.cuda.stream(user):
+        w.prime(seq[0])
+        w.step_batch(seq[1:], ov, cp)
+        hist[0].copy_(ov)
+        hist[1].copy_(cp)
+    user.synchronize()
+    st = w.graph_stats()
+    w.close()
+    assert st["batches"] == n
+    h = hist.cpu().numpy()
+    ref = oracle_lib.OracleFD(W, H)
+    ref.prime(clip91[0])
+    for t in range(n):
+        rov, rcp, _ = ref.step(clip91[t + 1])
+        assert np.array_equal(h[0, t], rov), f"overlay differs at frame {t + 1}"
+        assert np.array_equal(h[1, t], rcp), f"compressed differs at frame {t + 1}"
+    ref.close()
+
+
+def test_unfused_graph_per_frame_one_output_set(gpu_lib, oracle_lib, clip91, monkeypatch):
+    """block_size 8 (no fused front: the output stage alone writes the outputs),
+    24 per-frame graph calls into ONE output set with no caller's stream and no
+    sync between them: each batch's launch waits for the output stages of the
+    batches in flight that write the same bytes (fd_sched.h plan), so after
+    one sync the set holds the last frame's outputs."""
+    import torch
+    monkeypatch.setenv("DVC_FD_GRAPH", "1")
+    kw = dict(block_size=8, kernel_size=10, release_factor=0.3, quantization_level=100)
+    dev = torch.device("cuda", 0)
+    n = 24
+    seq = torch.from_numpy(clip91[:n + 1]).to(dev)
+    ov = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
+    cp = torch.zeros_like(ov)
+    w = gpu_lib.FDWorker(W, H, device=0, device_ptrs=True, **kw)
+    w.prime(seq[0])
+    for t in range(n):
+        w.step(seq[t + 1], ov, cp)
+    w.sync()
+    ovh, cph = ov.cpu().numpy(), cp.cpu().numpy()
+    st, gs, acc = w.stats(), w.graph_stats(), w.plane(gpu_lib._native.PLANE_ACC)
+    w.close()
+    assert gs["batches"] == n
+    ref = oracle_lib.OracleFD(W, H, **kw)
+    ref.prime(clip91[0])
+    for t in range(n):
+        rov, rcp, racc = ref.step(clip91[t + 1])
+    assert np.array_equal(ovh, rov), "overlay is not the last frame's"
+    assert np.array_equal(cph, rcp), "compressed is not the last frame's"
+    assert st == ref.stats()
+    assert np.array_equal(acc, racc)
     ref.close()
 
 
